@@ -15,7 +15,16 @@ Usage: python bench.py --gpus N --steps K --warmup W
 N > 1: one rank per GPU over RCCL -- either launched by torch.distributed.run (WORLD_SIZE / RANK / LOCAL_RANK in the environment),
 or, when WORLD_SIZE is not set, bench.py starts the N ranks itself (and fails loudly if the node has fewer than N GPUs); the
 line then carries comm_ms / exposed_comm_ms / comm_breakdown_ms / rccl_version / rccl_env.
-Prints ONE JSON line on rank 0.  At N = 1 the default line also carries `configs`: short runs of the other BASELINE configs.
+Prints ONE JSON line on rank 0.  A plain run sets up, conditions, warms up, times K steps and prints the line (the per-kernel and
+roofline figures come from events inside those same steps).  --full adds everything that takes runs of its own: the CPU baseline,
+the same K steps without the prefetched march, at N = 1 `configs` (short runs of the other BASELINE configs), at N > 1 the
+collective-free re-run behind exposed_comm_ms and the exchange variants.
+--dump-outputs DIR (trainer path) writes what the timed path computes in the last timed step (per-ray outputs, sample counts,
+loss, updated parameters) as DIR/<name>.npy in float32 / float64, every array of a fixed shape.  The fast path's float-atomic
+summation order differs from run to run and, over many steps, that grows past rounding; so after the line is measured the state
+the warm-up started from (left by the deterministic conditioning) is restored, the steps before the last one are run again in the
+trainer's deterministic mode, and the last step (same batch, same step index) runs on the timed path.  Per-ray outputs and loss
+are the same in every run, the parameters the same up to that one step's rounding.
 """
 import argparse
 import gc
@@ -125,7 +134,87 @@ def parse(argv=None):
                     help="N = 1, default headline config only: skip the short runs of the other BASELINE configs that are attached "
                          "to the line as `configs` (C2 with a bf16 table, C5 half2, C3 Garden shape, 65 536 rays, initialisation regime)")
     ap.add_argument("--configs-steps", type=int, default=20, help="timed steps of each `configs` entry")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the CPU baseline, the no-prefetch re-run, `configs` (N = 1) or the "
+                         "collective-free re-run and the exchange variants (N > 1); --no-cpu-baseline / --no-configs still apply")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path computes in the last timed step, from a reproducible state (the steps before it re-run "
+                         "in the trainer's deterministic mode after the measurement), as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.path != "trainer" or args.graph):
+        ap.error("--dump-outputs needs the trainer path without --graph (its deterministic mode makes the outputs reproducible)")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22          # an array with more elements is written as this many of them, at fixed seeded positions
+
+
+def _to_host(t):
+    return t.detach().float().cpu().numpy() if t.is_floating_point() else t.detach().cpu().numpy().astype(np.float64)
+
+
+def capture_outputs(res, model, loss):
+    """What a caller of a training step receives from it, on the host, in arrays whose shapes depend on the configuration only:
+    the step's per-ray results and sample counts (marched samples per ray in ray order: the march may pack rays in block-completion
+    order), the loss and the updated parameters.  The per-sample arrays are left out (their length is the step's sample count)."""
+    out = {}
+    for k in ("rgb", "opacity", "depth", "sq_err", "vr_per_ray", "rm_samples", "vr_samples"):
+        v = res.get(k) if hasattr(res, "get") else None
+        if isinstance(v, torch.Tensor):
+            out[k] = _to_host(v)
+    ra = res.get("rays_a") if hasattr(res, "get") else None
+    if isinstance(ra, torch.Tensor):
+        ra = ra.detach().cpu().numpy().astype(np.int64)
+        out["samples_per_ray"] = ra[np.argsort(ra[:, 0], kind="stable"), 2].astype(np.float64)
+    out["loss"] = np.array([loss], np.float64)
+    out["hash_table"] = _to_host(model.pos_encoder.hash_table)
+    out["mlp_weights"] = np.concatenate([_to_host(w).reshape(-1) for w in model._mlp_weights()])
+    return out
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy per array, float32 / float64; an array of more than DUMP_SAMPLE elements is written as a fixed, seeded sample
+    of them (flattened, positions ascending: the same positions in every run of the same configuration)."""
+    ready = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.size > DUMP_SAMPLE:
+            pick = np.sort(np.random.default_rng(20260).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[pick]
+        ready[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in ready.values())
+    if total > DUMP_LIMIT_BYTES:                        # (checked before anything is written: no partial dump)
+        raise SystemExit("--dump-outputs: %d bytes, more than %d" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in ready.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def snapshot_training_state(model, trainer):
+    """Everything a training step reads or advances: parameters and buffers, the optimizer's state, the live-sample counters and
+    the step parity, the RNG streams the march and the occupancy update draw from.  (trainer.state_dict() is collective at N > 1.)"""
+    return {"model": {k: v.detach().clone() for k, v in model.state_dict().items()}, "trainer": trainer.state_dict(),
+            "live": trainer._live_pair.clone(), "cur": trainer._cur,
+            "rng": (torch.get_rng_state(), torch.cuda.get_rng_state(trainer.dev), np.random.get_state())}
+
+
+def restore_training_state(model, trainer, snap):
+    sd = model.state_dict()
+    for k, v in snap["model"].items():
+        sd[k].copy_(v)                                  # (parameters are views of the trainer's storage: written in place)
+    trainer.load_state_dict(snap["trainer"])            # moments, scaler, schedule; clears gradients, refreshes the fp16 images
+    trainer._live_pair.copy_(snap["live"])
+    trainer._cur = snap["cur"]
+    for sets in trainer._sets.values():                 # no march prefetched in the measured run may be consumed
+        for M in sets:
+            M.src = None
+    torch.set_rng_state(snap["rng"][0])
+    torch.cuda.set_rng_state(snap["rng"][1], trainer.dev)
+    np.random.set_state(snap["rng"][2])
 
 
 class KernelTimer:
@@ -316,9 +405,10 @@ def main():
     if os.environ.get("NGP_BENCH_CHILD") == "1" and os.environ.get("NGP_BENCH_CHILD_CRASH") == "1":
         os.abort()                                  # (tests: an isolated leg that dies like a device fault would make it die)
     out = measure(args, ctx)
-    if rank == 0 and world == 1 and args.configs and _is_headline(args):
+    if rank == 0 and world == 1 and args.full and args.configs and _is_headline(args):
         out["configs"] = other_configs(args, ctx)
-    if world > 1 and args.configs and _is_headline(args) and args.comm in ("auto", "f32") and args.shard and "comm_overlap" not in os.environ.get("NGP_EXPERIMENT", ""):
+    if (world > 1 and args.full and args.configs and _is_headline(args) and args.comm in ("auto", "f32") and args.shard
+            and "comm_overlap" not in os.environ.get("NGP_EXPERIMENT", "")):
         # ONE invocation decides the multi-GPU defaults: the other exchange variants run in the same process group, behind the headline
         # The variants have never met a real multi-GPU node (no SCALE run in five rounds): the headline must survive one of them
         # hanging.  Every rank arms a watchdog for the variants phase (NGP_BENCH_VARIANT_TIMEOUT seconds, default 240): when it fires,
@@ -460,7 +550,8 @@ def _isolated_leg(args, ctx, extra, timeout_s):
     env["MASTER_PORT"] = str(port[0])
     env["NGP_BENCH_CHILD"] = "1"
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--condition", str(args.condition), "--kernel-events-every", str(args.kernel_events_every), "--no-cpu-baseline", "--no-configs"] + extra
+           "--condition", str(args.condition), "--kernel-events-every", str(args.kernel_events_every), "--full", "--no-cpu-baseline",
+           "--no-configs"] + extra
     try:
         res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout_s)
     except subprocess.TimeoutExpired:
@@ -481,7 +572,7 @@ def comm_variants(args, ctx, headline, progress=None):
                                 "in line on the step's stream", [], {}, headline, world))
     for name, what, extra, env in COMM_VARIANTS:
         sub = parse(["--gpus", str(world), "--steps", str(args.steps), "--warmup", str(args.warmup), "--condition", str(args.condition),
-                     "--kernel-events-every", str(args.kernel_events_every), "--no-cpu-baseline", "--no-configs"] + extra)
+                     "--kernel-events-every", str(args.kernel_events_every), "--full", "--no-cpu-baseline", "--no-configs"] + extra)
         saved = {k: os.environ.get(k) for k in env}
         os.environ.update(env)
         if progress is not None:
@@ -684,7 +775,7 @@ def _measure(args, ctx, brief):
 
     ev_every = max(1, min(args.kernel_events_every, args.steps // 3))        # (a short run still samples three steps)
 
-    def trainer_step(i, prefetch=True, log=True):
+    def trainer_step(i, prefetch=True, log=True, grid=True):
         rays_o, rays_d, target = pool[i % n_pool]
         # per-kernel events on every ev_every-th step; an occupancy-update step (its 1 M-point encodes go through the same entry
         # points) hands its turn to the next step, so that the per-kernel averages are those of the training step's launches
@@ -692,11 +783,12 @@ def _measure(args, ctx, brief):
         due = state["k"] % ee == ee // 2 or state.get("ev_owed", False)
         timer.sample = due and i % 16 != 0
         state["ev_owed"] = due and i % 16 == 0
-        if i % 16 == 0:
+        if i % 16 == 0 and grid:
             grid_update(i)
         nxt = pool[(i + 1) % n_pool]
         pre = (nxt[0], nxt[1]) if (prefetch and (i + 1) % 16 != 0) else None      # never across a grid update
         out = trainer.step(rays_o, rays_d, target, prefetch=pre)
+        state["last"] = out
         k = state["k"]
         if log and k % STAT_EVERY == 0 and k // STAT_EVERY < stat_log.shape[0]:
             stat_log[k // STAT_EVERY, 0].copy_(out["rm_samples"][0])
@@ -709,9 +801,9 @@ def _measure(args, ctx, brief):
             live_log[k // STAT_EVERY, 0].copy_(trainer._live_total[0])
         state["k"] = k + 1
 
-    def step(i, prefetch=True, log=True):
+    def step(i, prefetch=True, log=True, grid=True):
         if use_trainer:
-            return trainer_step(i, prefetch, log)
+            return trainer_step(i, prefetch, log, grid)
         rays_o, rays_d, target = pool[i % n_pool]
         with torch.autocast(device_type="cuda", dtype=torch.float16):
             if i % 16 == 0:
@@ -757,6 +849,8 @@ def _measure(args, ctx, brief):
         fence()
         t_cond = time.perf_counter() - t0
         base = args.condition
+    # --dump-outputs: the state the warm-up starts from (after the conditioning, which runs in deterministic mode: the same in every run)
+    snap = snapshot_training_state(model, trainer) if args.dump_outputs else None
     if not os.environ.get("NGP_BENCH_KEEP_GC"):
         # a generation-2 pass of the cyclic collector over the process's long-lived objects takes 36 ms here (measured with
         # --step-trace), 55 steps' worth; where the next one lands depends on the allocation count so far.  Collect now and freeze
@@ -837,7 +931,7 @@ def _measure(args, ctx, brief):
     # ---- after the timed region (untimed, informational): the same K steps again with the march NOT prefetched, i.e. what a
     # loop pays whose next batch is not known one step ahead
     elapsed_np = None
-    if use_trainer and args.prefetch and not args.graph and world == 1 and not brief:
+    if use_trainer and args.prefetch and not args.graph and world == 1 and args.full and not brief:
         i0 = base + args.warmup + args.steps
         i0 += (-i0) % 16                                                    # same phase relative to the grid updates ...
         i0 += (base + args.warmup) % 16                                     # ... as the timed region
@@ -854,7 +948,7 @@ def _measure(args, ctx, brief):
     elapsed_stub = None
     # (the stubbed steps below let the ranks drift apart: everything the line reports about the model's state is read before them)
     loss_at_end = trainer.last_loss() if (use_trainer and scene) else None
-    if use_trainer and world > 1 and not args.graph and not brief:
+    if use_trainer and world > 1 and not args.graph and args.full and not brief:
         i0 = base + args.warmup + args.steps
         i0 += (-i0) % 16
         i0 += (base + args.warmup) % 16
@@ -1095,7 +1189,7 @@ def _measure(args, ctx, brief):
         }
         if world > 1:
             out.update(comm_fields(trainer if use_trainer else None, dict(ctx, ms_per_step=out.get("ms_per_step")), args))
-        if not args.no_cpu_baseline and world == 1 and not garden:     # the CPU leg restates the C2 workload only
+        if args.full and not args.no_cpu_baseline and world == 1 and not garden:     # the CPU leg restates the C2 workload only
             if scene:
                 out["cpu_baseline"] = cpu_baseline(model.density_bitfield.cpu().numpy(), args.cpu_seconds,
                                                    table=model.pos_encoder.hash_table.detach().float().view(-1).cpu().numpy(),
@@ -1103,6 +1197,33 @@ def _measure(args, ctx, brief):
             else:
                 out["cpu_baseline"] = cpu_baseline(bits_np if args.regime == "lego" else np.load(golden)["density_bitfield"],
                                                    args.cpu_seconds)
+    if snap is not None:
+        # --dump-outputs, after everything the line reports.  The fast path's float-atomic summation order differs from run to run, and
+        # over many steps (an occupancy update thresholds the densities) that grows past rounding: the state the timed loop's last step
+        # started from is not reproducible.  So: back to the state the warm-up started from, the steps before the last one again on the
+        # same batches and step indices (grid updates included) in the trainer's deterministic mode -- a reproducible state -- and then
+        # the last step itself on the timed path (one-launch march, fused live list, replicated scatter-add plan); its outputs are
+        # written.  Per-ray results and the loss are then the same in every run, the updated parameters the same up to the rounding of
+        # that one step's float atomics.
+        restore_training_state(model, trainer, snap)
+        del snap
+        last = base + args.warmup + args.steps - 1
+        trainer.set_deterministic(True)
+        fence()
+        for i in range(base, last):
+            step(i, prefetch=args.prefetch, log=False)
+        if last % 16 == 0:
+            grid_update(last)                             # (the fast occupancy update scatters without a max: not reproducible)
+        for sets in trainer._sets.values():               # the last step marches its own rays, on the timed path
+            for M in sets:
+                M.src = None
+        fence()
+        trainer.set_deterministic(False)
+        step(last, prefetch=args.prefetch, log=False, grid=False)
+        fence()
+        trainer.sync_master()                             # (N > 1: collective, every rank)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, capture_outputs(state["last"], model, trainer.last_loss()))
     return out
 
 

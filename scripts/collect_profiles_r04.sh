@@ -9,12 +9,12 @@ set -u
 OUT=gpurun_out/${1:-r04_collect}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-python bench.py --steps 20 --warmup 5 > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"
-python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-configs > "$OUT/bench_steps200.json" 2>/dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-configs > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"
+python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-configs > "$OUT/bench_steps200.json" 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-configs > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
 pass() {   # name, counters...
   local name=$1; shift
-  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/pmc_$name" -o p -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-configs > "$OUT/pmc_${name}_bench.json" 2> "$OUT/pmc_$name.err"
+  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$OUT/pmc_$name" -o p -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-configs > "$OUT/pmc_${name}_bench.json" 2> "$OUT/pmc_$name.err"
   local csv=$(find "$OUT/pmc_$name" -name "*counter_collection.csv" | head -1)
   python profiles/pmc_summarize.py --tail 25 "ngp" "$csv" > "$OUT/pmc_$name.json"
   rm -rf "$OUT/pmc_$name"

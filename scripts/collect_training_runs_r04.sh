@@ -13,7 +13,7 @@ run _distortion --max_steps 5000 --extra="--distortion_loss_w 1e-3"
 run _half --max_steps 20000 --extra=--half_opt
 run _garden --scene garden --wh 200 --batch_size 4096 --max_steps 20000 --extra="--distortion_loss_w 1e-3"
 run _torch_adam --env "NGP_NO_APEX=1"
-NGP_BENCH_BACKEND=gloo NGP_BENCH_ONE_DEVICE=1 timeout 300 python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_2ranks_gloo_one_gpu.json 2> /dev/null
-NGP_COMM_OVERLAP=1 NGP_BENCH_BACKEND=gloo NGP_BENCH_ONE_DEVICE=1 timeout 300 python bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_2ranks_gloo_one_gpu_overlap.json 2> /dev/null
+NGP_BENCH_BACKEND=gloo NGP_BENCH_ONE_DEVICE=1 timeout 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_2ranks_gloo_one_gpu.json 2> /dev/null
+NGP_COMM_OVERLAP=1 NGP_BENCH_BACKEND=gloo NGP_BENCH_ONE_DEVICE=1 timeout 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 > $O/bench_2ranks_gloo_one_gpu_overlap.json 2> /dev/null
 timeout 1500 python -m pytest tests -m gpu -q --timeout 300 > $O/pytest_gpu.log 2>&1; tail -3 $O/pytest_gpu.log
 ls $O

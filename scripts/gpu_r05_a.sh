@@ -6,11 +6,11 @@ export TMPDIR=/tmp
 O=gpurun_out/r05a; mkdir -p $O
 timeout 600 python -m pytest tests/test_gpu_flush_adam.py -x -q 2>&1 | tail -25 > $O/pytest_flush.txt
 timeout 900 python -m pytest tests -m gpu -q 2>&1 | tail -40 > $O/pytest_gpu.txt
-timeout 300 python bench.py --steps 20 --warmup 5 > $O/bench_default_1.json 2> $O/bench_default_1.err
-timeout 300 python bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_default_2.json 2> $O/bench_default_2.err
-NGP_FLUSH_ADAM=0 timeout 300 python bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_two_launch.json 2> $O/bench_two_launch.err
-timeout 300 python bench.py --steps 200 --warmup 20 --no-configs --no-cpu-baseline > $O/bench_steps200.json 2> $O/bench_steps200.err
-NGP_FLUSH_ADAM=0 timeout 300 python bench.py --steps 200 --warmup 20 --no-configs --no-cpu-baseline > $O/bench_steps200_two_launch.json 2> $O/bench_steps200_two_launch.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_default_1.json 2> $O/bench_default_1.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_default_2.json 2> $O/bench_default_2.err
+NGP_FLUSH_ADAM=0 timeout 300 python bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_two_launch.json 2> $O/bench_two_launch.err
+timeout 300 python bench.py --full --steps 200 --warmup 20 --no-configs --no-cpu-baseline > $O/bench_steps200.json 2> $O/bench_steps200.err
+NGP_FLUSH_ADAM=0 timeout 300 python bench.py --full --steps 200 --warmup 20 --no-configs --no-cpu-baseline > $O/bench_steps200_two_launch.json 2> $O/bench_steps200_two_launch.err
 tail -3 $O/pytest_flush.txt $O/pytest_gpu.txt
 for f in $O/bench_*.json; do python - "$f" <<'PY'
 import json,sys

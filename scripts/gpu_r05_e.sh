@@ -5,9 +5,9 @@ export TMPDIR=/tmp
 O=gpurun_out/r05e; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_chunked.py tests/test_gpu_flush_adam.py -q -x 2>&1 | tail -30 > $O/pytest_chunked.txt
 timeout 600 python -m pytest tests/test_gpu_bench_contract.py tests/test_gpu_configs.py -q 2>&1 | tail -30 > $O/pytest_bench.txt
-timeout 300 python bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err
-timeout 300 python bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline --scene garden --condition 512 > $O/bench_garden_chunked.json 2> $O/bench_garden_chunked.err
-NGP_CHUNKED_FWD=0 timeout 300 python bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline --scene garden --condition 512 > $O/bench_garden_all.json 2> $O/bench_garden_all.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline > $O/bench_default.json 2> $O/bench_default.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline --scene garden --condition 512 > $O/bench_garden_chunked.json 2> $O/bench_garden_chunked.err
+NGP_CHUNKED_FWD=0 timeout 300 python bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline --scene garden --condition 512 > $O/bench_garden_all.json 2> $O/bench_garden_all.err
 tail -n 12 $O/pytest_chunked.txt $O/pytest_bench.txt
 for f in $O/bench_*.json; do python - "$f" <<'PY'
 import json,sys

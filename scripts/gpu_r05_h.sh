@@ -7,7 +7,7 @@ O=gpurun_out/r05h; mkdir -p $O
 timeout 1200 python -m pytest tests/test_gpu_apex_adam.py tests/test_gpu_chunked.py tests/test_gpu_e2e_state.py tests/test_gpu_fused.py tests/test_dropin_imports.py tests/test_gpu_half_fused.py -q --tb=short 2>&1 | tail -60 > $O/pytest_sel.txt
 timeout 300 python scripts/run_reference_train.py --max_steps 4000 --wh 400 --n_train 25 --n_test 2 --cprofile $O/train_py_cprofile.txt --out $O/reference_train_py_cprofile_run.json > $O/ref_train_cprof.out 2>&1
 timeout 600 python scripts/run_reference_train.py --out $O/reference_train_py.json --log $O/reference_train_py.log > $O/ref_train.out 2>&1
-timeout 300 python bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline --path modules > $O/bench_modules.json 2> $O/bench_modules.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline --path modules > $O/bench_modules.json 2> $O/bench_modules.err
 export NGP_HIPCC_EXTRA="-DNGP_BWD_DIAG -DNGP_HASH_FWD_DIAG"
 timeout 600 python -c "
 import sys; sys.path.insert(0, 'taichi-nerfs_amd')

@@ -5,9 +5,9 @@ export TMPDIR=/tmp
 O=gpurun_out/r05i; mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -40 > $O/pytest_gpu.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" > $O/smoke.txt 2>&1
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err
-timeout 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-configs > $O/bench_steps200.json 2> /dev/null
-timeout 300 python bench.py > $O/bench_noflags.json 2> /dev/null
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_steps20.json 2> $O/bench_steps20.err
+timeout 300 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-configs > $O/bench_steps200.json 2> /dev/null
+timeout 300 python bench.py --full > $O/bench_noflags.json 2> /dev/null
 tail -n 6 $O/pytest_gpu.txt; tail -2 $O/smoke.txt
 for f in $O/bench_*.json; do python - "$f" <<'PY'
 import json,sys

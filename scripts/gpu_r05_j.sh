@@ -7,7 +7,7 @@ timeout 1200 python -m pytest tests/test_gpu_fused.py tests/test_gpu_half_fused.
 timeout 300 python scripts/run_reference_train.py --max_steps 4000 --wh 400 --n_train 25 --n_test 2 --cprofile $O/train_py_cprofile.txt --out $O/reference_train_py_cprofile_run.json > $O/ref_train_cprof.out 2>&1
 timeout 600 python scripts/run_reference_train.py --out $O/reference_train_py.json --log $O/reference_train_py.log > $O/ref_train.out 2>&1
 timeout 600 python scripts/run_reference_train.py --extra "--half_opt" --out $O/reference_train_py_half.json --log $O/reference_train_py_half.log > $O/ref_train_half.out 2>&1
-timeout 300 python bench.py --steps 20 --warmup 5 --no-configs --no-cpu-baseline --path modules > $O/bench_modules.json 2> $O/bench_modules.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-configs --no-cpu-baseline --path modules > $O/bench_modules.json 2> $O/bench_modules.err
 tail -n 8 $O/pytest_sel.txt
 grep -n "grad_scaler.py:360\|rendering.py:104\|run_backward\|fused.py.*forward\|fused.py.*backward\|optimizers.py.*step" $O/train_py_cprofile.txt | head
 python - <<'PY'

@@ -6,7 +6,7 @@ O=gpurun_out/r05m; mkdir -p $O
 B="--steps 200 --warmup 20 --no-configs --no-cpu-baseline"
 for cfg in "48 8 128" "48 16 128" "48 16 512" "48 8 512" "48 16 256" "48 8 128" "48 16 128" "48 16 512" "48 8 512" "48 16 256" "48 8 128" "48 16 128" "48 16 512" "48 8 512" "48 16 256"; do
   set -- $cfg
-  NGP_BWD_REP_TARGET=$1 NGP_BWD_DENSE_MIN_REP=$2 NGP_BWD_MERGE_RES=$3 timeout 300 python bench.py $B > $O/b_$1_$2_$3.json 2>/dev/null
+  NGP_BWD_REP_TARGET=$1 NGP_BWD_DENSE_MIN_REP=$2 NGP_BWD_MERGE_RES=$3 timeout 300 python bench.py --full $B > $O/b_$1_$2_$3.json 2>/dev/null
   python - "$O/b_$1_$2_$3.json" "$cfg" <<'PY'
 import json,sys
 try:

@@ -11,7 +11,7 @@ for e in 4 0 8 4 0 8; do
 import sys; sys.path.insert(0, 'taichi-nerfs_amd')
 from ngp_hip import lib; lib.build()" > /dev/null 2>&1
   for rep in 1 2; do
-    timeout 300 python bench.py $B > $O/b_${e}_$rep.json 2>/dev/null
+    timeout 300 python bench.py --full $B > $O/b_${e}_$rep.json 2>/dev/null
     python - "$O/b_${e}_$rep.json" "$e" <<'PY'
 import json,sys
 try:

@@ -5,10 +5,10 @@ export TMPDIR=/tmp
 O=gpurun_out/r05r; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_chunked.py tests/test_gpu_configs.py tests/test_gpu_trainer.py -q --tb=short 2>&1 | tail -15 > $O/pytest_sel.txt
 G="--steps 20 --warmup 5 --no-configs --no-cpu-baseline --scene garden --condition 512"
-timeout 300 python bench.py $G > $O/garden_default.json 2> $O/err.txt
-NGP_PREFETCH_AT=2 NGP_MARCH_SHAPE=16,0 NGP_SIDE_PRIORITY=low timeout 300 python bench.py $G > $O/garden_pos2_w16_low.json 2>> $O/err.txt
-NGP_PREFETCH_AT=1 NGP_MARCH_SHAPE=16,0 NGP_SIDE_PRIORITY=low timeout 300 python bench.py $G > $O/garden_pos1_w16_low.json 2>> $O/err.txt
-timeout 300 python bench.py $G > $O/garden_default_2.json 2>> $O/err.txt
+timeout 300 python bench.py --full $G > $O/garden_default.json 2> $O/err.txt
+NGP_PREFETCH_AT=2 NGP_MARCH_SHAPE=16,0 NGP_SIDE_PRIORITY=low timeout 300 python bench.py --full $G > $O/garden_pos2_w16_low.json 2>> $O/err.txt
+NGP_PREFETCH_AT=1 NGP_MARCH_SHAPE=16,0 NGP_SIDE_PRIORITY=low timeout 300 python bench.py --full $G > $O/garden_pos1_w16_low.json 2>> $O/err.txt
+timeout 300 python bench.py --full $G > $O/garden_default_2.json 2>> $O/err.txt
 tail -n 6 $O/pytest_sel.txt
 for f in $O/garden_*.json; do python - "$f" <<'PY'
 import json,sys

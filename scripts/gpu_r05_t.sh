@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r05t2; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_chunked.py tests/test_gpu_flush_adam.py -q --tb=short -k "sliced or chunked or flush" 2>&1 | tail -5 > $O/pytest_sel.txt
 G="--steps 20 --warmup 5 --no-configs --no-cpu-baseline --scene garden --condition 512"
-run() { name=$1; shift; env "$@" timeout 300 python bench.py $G > $O/garden_$name.json 2>> $O/err.txt; }
+run() { name=$1; shift; env "$@" timeout 300 python bench.py --full $G > $O/garden_$name.json 2>> $O/err.txt; }
 run adaptive X=1
 run at3_low NGP_PREFETCH_AT=3 NGP_SIDE_PRIORITY=low
 run at3_def NGP_PREFETCH_AT=3 NGP_SIDE_PRIORITY=default

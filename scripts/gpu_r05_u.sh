@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r05u; mkdir -p $O
 G="--steps 20 --warmup 5 --no-configs --no-cpu-baseline --scene garden --condition 512"
-run() { name=$1; shift; env "$@" timeout 300 python bench.py $G > $O/garden_$name.json 2>> $O/err.txt; }
+run() { name=$1; shift; env "$@" timeout 300 python bench.py --full $G > $O/garden_$name.json 2>> $O/err.txt; }
 run adaptive_a X=1
 run at25_low_w4_a NGP_PREFETCH_AT=2.5 NGP_SIDE_PRIORITY=low NGP_MARCH_SHAPE=4,0
 run at0_low_w4 NGP_PREFETCH_AT=0 NGP_SIDE_PRIORITY=low NGP_MARCH_SHAPE=4,0

@@ -5,8 +5,8 @@ export TMPDIR=/tmp
 O=gpurun_out/r05v; mkdir -p $O
 timeout 120 python -m pytest tests/test_gpu_trainer.py -q --tb=short -x -k "placement or prefetch" 2>&1 | tail -15 > $O/pytest_sel.txt
 H="--steps 20 --warmup 5 --no-configs --no-cpu-baseline"
-timeout 100 python bench.py $H --regime random50 > $O/init_rule.json 2> $O/err.txt
-timeout 100 python bench.py $H --rays 65536 > $O/lego65536_rule.json 2>> $O/err.txt
+timeout 100 python bench.py --full $H --regime random50 > $O/init_rule.json 2> $O/err.txt
+timeout 100 python bench.py --full $H --rays 65536 > $O/lego65536_rule.json 2>> $O/err.txt
 tail -n 6 $O/pytest_sel.txt
 for f in $O/*.json; do python - "$f" <<'PY'
 import json,sys

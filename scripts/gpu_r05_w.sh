@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
 O=gpurun_out/r05w; mkdir -p $O
 timeout 60 python -m pytest tests/test_gpu_trainer.py tests/test_gpu_configs.py -q --tb=short -x -k "placement or prefetch or garden or c3 or C3" 2>&1 | tail -8 > $O/pytest_sel.txt
-timeout 110 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20_nocpu.json 2> $O/err.txt
+timeout 110 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20_nocpu.json 2> $O/err.txt
 tail -n 3 $O/pytest_sel.txt
 python - $O/bench_steps20_nocpu.json <<'PY'
 import json,sys

@@ -1,6 +1,9 @@
-"""Drop-in check available only where the reference checkout exists (this build container, not the GPU box): the
-reference's UNCHANGED train.py (and through it gui.py, datasets/, opt.py) imports against this repo's `modules`
-package + the import-only stand-ins in taichi-nerfs_amd/compat/."""
+"""Drop-in checks.  Where the reference checkout exists: the reference's UNCHANGED train.py (and through it gui.py, datasets/,
+opt.py) imports against this repo's `modules` package + the import-only stand-ins in taichi-nerfs_amd/compat/.  Everywhere: the
+public callables have the reference's parameter names (read from the checkout where it exists and held to
+tests/golden/ref_driver_shape.json, read from that file elsewhere)."""
+import ast
+import json
 import os
 import subprocess
 import sys
@@ -10,6 +13,29 @@ import pytest
 from conftest import ROOT
 
 REF = "/root/reference"
+DRIVER_SHAPE = os.path.join(ROOT, "tests", "golden", "ref_driver_shape.json")
+# (file under modules/, public callables) and (file, class whose __init__ parameters are compared)
+FUNCTIONS = [("intersection.py", ["ray_aabb_intersection"]), ("ray_march.py", ["raymarching_train", "raymarching_test"]),
+             ("volume_render_test.py", ["composite_test"]), ("rendering.py", ["render"]), ("distortion.py", ["distortion_loss"])]
+CLASSES = [("networks.py", "NGP"), ("networks.py", "MLP"), ("hash_encoder.py", "HashEncoder"), ("hash_encoder_half.py", "HashEncoder")]
+
+
+def reference_signatures(root):
+    """Parameter names, in order, of the reference's public callables and class constructors under root/modules."""
+    funcs, classes = {}, {}
+    for fname, names in FUNCTIONS:
+        sigs = {}
+        for node in ast.walk(ast.parse(open(os.path.join(root, "modules", fname)).read())):
+            if isinstance(node, ast.FunctionDef):
+                sigs.setdefault(node.name, [a.arg for a in node.args.args])
+        funcs[fname] = {n: sigs[n] for n in names}
+    for fname, cname in CLASSES:
+        tree = ast.parse(open(os.path.join(root, "modules", fname)).read())
+        for node in tree.body:
+            if isinstance(node, ast.ClassDef) and node.name == cname:
+                init = [f for f in node.body if isinstance(f, ast.FunctionDef) and f.name == "__init__"][0]
+                classes["%s:%s" % (fname, cname)] = [a.arg for a in init.args.args]
+    return {"functions": funcs, "classes": classes}
 
 
 @pytest.mark.skipif(not os.path.exists(os.path.join(REF, "train.py")), reason="reference checkout not present")
@@ -29,38 +55,23 @@ def test_reference_train_py_imports_our_modules():
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, "modules")), reason="reference checkout not present")
 def test_public_signatures_match_reference():
     """Same parameter names (and order) for every public callable of the boundary."""
-    import ast
     import inspect
-
-    def ref_sigs(path):
-        tree = ast.parse(open(path).read())
-        out = {}
-        for node in ast.walk(tree):
-            if isinstance(node, ast.FunctionDef):
-                out.setdefault(node.name, [a.arg for a in node.args.args])
-        return out
-
+    stored = json.load(open(DRIVER_SHAPE))["signatures"]
+    if os.path.exists(os.path.join(REF, "modules")):
+        assert reference_signatures(REF) == stored
     import modules.intersection as mi, modules.ray_march as mr, modules.volume_render_test as mv, modules.rendering as rd
     import modules.networks as nw, modules.hash_encoder as he, modules.hash_encoder_half as hh, modules.distortion as ds
-    checks = [("intersection.py", mi, ["ray_aabb_intersection"]), ("ray_march.py", mr, ["raymarching_train", "raymarching_test"]),
-              ("volume_render_test.py", mv, ["composite_test"]), ("rendering.py", rd, ["render"]),
-              ("distortion.py", ds, ["distortion_loss"])]
-    for fname, mod, names in checks:
-        ref = ref_sigs(os.path.join(REF, "modules", fname))
+    mods = {"intersection.py": mi, "ray_march.py": mr, "volume_render_test.py": mv, "rendering.py": rd, "distortion.py": ds,
+            "networks.py": nw, "hash_encoder.py": he, "hash_encoder_half.py": hh}
+    for fname, names in FUNCTIONS:
         for n in names:
-            assert list(inspect.signature(getattr(mod, n)).parameters) == ref[n], (fname, n)
+            assert list(inspect.signature(getattr(mods[fname], n)).parameters) == stored["functions"][fname][n], (fname, n)
     # class constructors
-    for fname, cls in (("networks.py", nw.NGP), ("networks.py", nw.MLP), ("hash_encoder.py", he.HashEncoder),
-                       ("hash_encoder_half.py", hh.HashEncoder)):
-        tree = ast.parse(open(os.path.join(REF, "modules", fname)).read())
-        for node in tree.body:
-            if isinstance(node, ast.ClassDef) and node.name == cls.__name__:
-                init = [f for f in node.body if isinstance(f, ast.FunctionDef) and f.name == "__init__"][0]
-                ours = inspect.signature(cls.__init__).parameters
-                ref_args = [a.arg for a in init.args.args]
-                # every reference parameter, same order; extensions only as trailing keyword arguments with defaults
-                assert list(ours)[:len(ref_args)] == ref_args, (fname, cls)
-                assert all(ours[k].default is not inspect.Parameter.empty for k in list(ours)[len(ref_args):]), (fname, cls)
+    for fname, cname in CLASSES:
+        ours = inspect.signature(getattr(mods[fname], cname).__init__).parameters
+        ref_args = stored["classes"]["%s:%s" % (fname, cname)]
+        # every reference parameter, same order; extensions only as trailing keyword arguments with defaults
+        assert list(ours)[:len(ref_args)] == ref_args, (fname, cname)
+        assert all(ours[k].default is not inspect.Parameter.empty for k in list(ours)[len(ref_args):]), (fname, cname)

@@ -1,6 +1,6 @@
 """bench.py's output contract (one JSON line on stdout; metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-higher_is_better / scaling / vs_baseline / dtype / data / config.workload + the `roofline` and `cpu_baseline` objects) on a short
-run of the real thing: a fresh process, a small conditioning, 6 timed steps."""
+higher_is_better / scaling / vs_baseline / dtype / data / config.workload + the `roofline` object, and with --full the `cpu_baseline`
+object) on a short run of the real thing: a fresh process, a small conditioning, 6 timed steps."""
 import json
 import os
 import subprocess
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_contract(hip_lib):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--condition", "48", "--cpu-seconds", "1",
-           "--kernel-events-every", "2", "--no-configs"]
+           "--kernel-events-every", "2", "--no-configs", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -38,10 +38,45 @@ def test_bench_line_contract(hip_lib):
     assert d["value"] > 10 * c["value"]
 
 
+def test_bench_plain_run_and_dumped_outputs(hip_lib, tmp_path):
+    """A plain run measures the headline only (no CPU baseline, no no-prefetch re-run, no `configs`); --dump-outputs writes what the
+    timed path computes in the last timed step as float32 / float64 .npy files, at most 64 MB in all.  Two runs of the same command
+    write the same per-ray outputs and loss bit for bit and the same parameters up to one step's float-atomic rounding, and the
+    dumped loss is the timed loop's last loss (`loss_at_end`) up to the few steps' difference between the two trajectories."""
+    import numpy as np
+    dumps = [tmp_path / "a", tmp_path / "b"]
+    for dump in dumps:
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--condition", "32",
+               "--dump-outputs", str(dump)]
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        loss = float(np.load(dump / "loss.npy")[0])
+        assert abs(loss - d["config"]["workload_state"]["loss_at_end"]) <= 0.05 * d["config"]["workload_state"]["loss_at_end"]
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 8192 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert "cpu_baseline" not in d and "configs" not in d and d["ms_per_step_no_prefetch"] is None
+    files = {f.name: np.load(f) for f in dumps[0].iterdir()}
+    again = {f.name: np.load(f) for f in dumps[1].iterdir()}
+    assert set(again) == set(files)
+    for k in files:
+        if k in ("hash_table.npy", "mlp_weights.npy"):
+            np.testing.assert_allclose(again[k], files[k], rtol=1e-5, atol=1e-7, err_msg=k)
+        else:
+            assert np.array_equal(again[k], files[k]), k
+    assert {"rgb.npy", "opacity.npy", "depth.npy", "loss.npy", "hash_table.npy", "mlp_weights.npy", "samples_per_ray.npy"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["rgb.npy"].shape == (8192, 3) and np.isfinite(files["rgb.npy"]).all() and np.isfinite(files["loss.npy"]).all()
+    assert files["samples_per_ray.npy"].shape == (8192,) and files["samples_per_ray.npy"].sum() > 0
+
+
 def test_bench_configs_array(hip_lib):
-    """the default N = 1 line carries short runs of the other BASELINE configs."""
+    """the --full N = 1 line carries short runs of the other BASELINE configs."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--condition", "32", "--no-cpu-baseline",
-           "--configs-steps", "4"]
+           "--configs-steps", "4", "--full"]
     env = dict(os.environ, NGP_BENCH_CONFIG_CONDITION="32")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -69,7 +104,7 @@ def test_bench_self_launches_two_ranks(hip_lib):
     """`python bench.py --gpus 2` WITHOUT torchrun starts two ranks by itself (here both on GPU 0 over gloo: a
     functional run of the N > 1 path, not a measurement) and the line carries the communication fields."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--condition", "32",
-           "--kernel-events-every", "2"]
+           "--kernel-events-every", "2", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NGP_BENCH_BACKEND="gloo", NGP_BENCH_ONE_DEVICE="1")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
@@ -112,7 +147,7 @@ def test_bench_two_ranks_watchdog_keeps_the_headline(hip_lib):
     takes longer) rank 0 still prints ONE line -- the headline leg, the variants completed so far, and `configs_incomplete` -- and every
     rank exits."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--condition", "32",
-           "--kernel-events-every", "2"]
+           "--kernel-events-every", "2", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NGP_BENCH_BACKEND="gloo", NGP_BENCH_ONE_DEVICE="1", NGP_BENCH_VARIANT_TIMEOUT="1")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
@@ -127,7 +162,7 @@ def test_bench_two_ranks_isolated_leg_may_die(hip_lib):
     """The direct peer-memory exchange runs in child processes of the ranks: children that abort (as a device fault would make them) leave
     ONE complete line -- the headline, every collective variant, and an `error` record for the leg that died."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--condition", "32",
-           "--kernel-events-every", "2"]
+           "--kernel-events-every", "2", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NGP_BENCH_BACKEND="gloo", NGP_BENCH_ONE_DEVICE="1", NGP_BENCH_CHILD_CRASH="1")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
@@ -145,7 +180,7 @@ def test_bench_two_ranks_overlapped_exchange(hip_lib):
     """NGP_EXPERIMENT comm_overlap=1: the scatter-add in one launch per level group, each group's reduce-scatter in flight under the next
     group's launch (functional run over gloo on one GPU; the line names the grouping and what the step waited for)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--condition", "32",
-           "--kernel-events-every", "2"]
+           "--kernel-events-every", "2", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(NGP_BENCH_BACKEND="gloo", NGP_BENCH_ONE_DEVICE="1", NGP_EXPERIMENT="comm_overlap=1;comm_groups=12,8,0")
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)

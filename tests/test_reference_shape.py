@@ -1,16 +1,19 @@
 """examples/train_reference_shape.py is a training driver written in this repo that uses the `modules` boundary exactly the way the
 reference's train.py does.  Two tests:
 
-  * structural (CPU; needs /root/reference, i.e. runs in the build container): both files are parsed and the ORDERED sequences of
-    boundary calls -- name, number of positional arguments, keyword names, whether inside `torch.autocast` -- of the training
+  * structural (CPU): both files are parsed and the ORDERED sequences of boundary calls -- name, number of positional arguments, keyword names, whether inside `torch.autocast` -- of the training
     iteration (train.py:168-201), of the optimizer / scaler / scheduler construction (:137-165) and of the evaluation loop (:237-262)
-    are compared.  The example cannot drift away from the shape of train.py without this failing;
+    are compared.  The example cannot drift away from the shape of train.py without this failing.  train.py's side is read from the
+    reference checkout where it exists (and held to tests/golden/ref_driver_shape.json, oracle/gen_golden_checkout.py), from that
+    file elsewhere;
   * executed (`-m gpu`; needs nothing but this repo): the example trains the procedural scene for 300 steps through render() + the
     compat FusedAdam + torch GradScaler and has to reach 20 dB on held-out views -- the drop-in loop runs on the driver's box, where
     the reference checkout (and with it tests/test_gpu_reference_train.py) is absent.
 """
 import ast
+import hashlib
 import importlib.util
+import json
 import os
 
 import pytest
@@ -19,12 +22,16 @@ from conftest import ROOT
 
 REF = "/root/reference/train.py"
 OURS = os.path.join(ROOT, "examples", "train_reference_shape.py")
+DRIVER_SHAPE = os.path.join(ROOT, "tests", "golden", "ref_driver_shape.json")
 
 # the calls that ARE the boundary + the optimisation protocol around it (attribute or plain name of the callee)
 LOOP_CALLS = {"train", "update_density_grid", "get_rays", "render", "mse_loss", "distortion_loss", "mean", "zero_grad", "scale", "backward",
               "step", "update", "autocast"}
 SETUP_CALLS = {"mark_invisible_cells", "GradScaler", "FusedAdam", "Adam", "CosineAnnealingLR", "parameters"}
 EVAL_CALLS = {"eval", "no_grad", "autocast", "get_rays", "render"}
+# constants the protocol hangs on
+NEEDLES = ("warmup_steps = 256", "update_interval = 16", "exp_step_factor = 1 / 256 if hparams.scale > 0.5 else 0.0",
+           "0.01 * MAX_SAMPLES / 3 ** 0.5", "step < warmup_steps", "step % update_interval == 0", "eps=1e-15", "hparams.lr / 30")
 
 
 def _callee(node):
@@ -89,42 +96,75 @@ def _main_parts(path):
     return main, setup, train_loop, eval_with
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present")
+def driver_structure(path):
+    """What the tests compare of a driver: the boundary-call sequences of its training iteration, setup and evaluation loop, its loop
+    bounds and which of NEEDLES it contains (JSON-shaped)."""
+    _, setup, loop, ev = _main_parts(path)
+    src = ast.unparse(ast.parse(open(path).read()))
+    d = {"loop": _events(loop.body, LOOP_CALLS), "setup": _events(setup, SETUP_CALLS), "eval": _events([ev], EVAL_CALLS),
+         "loop_iter": ast.unparse(loop.iter), "needles": [n for n in NEEDLES if n in src]}
+    return json.loads(json.dumps(d))
+
+
+def line_similarity(ref_path, ours_path):
+    """difflib ratio between the stripped non-empty lines of two files."""
+    import difflib
+    a = [x.strip() for x in open(ref_path).read().splitlines() if x.strip()]
+    b = [x.strip() for x in open(ours_path).read().splitlines() if x.strip()]
+    return difflib.SequenceMatcher(None, a, b).ratio()
+
+
+def example_similarity(ref_path):
+    """The example's line similarity with train.py, and the sha256 of the example file it was measured on."""
+    return {"example_sha256": hashlib.sha256(open(OURS, "rb").read()).hexdigest(), "line_similarity": line_similarity(ref_path, OURS)}
+
+
+def _reference_structure():
+    stored = json.load(open(DRIVER_SHAPE))["train_py"]
+    if os.path.exists(REF):
+        assert driver_structure(REF) == stored
+    return stored
+
+
 def test_example_has_the_call_structure_of_train_py():
-    _, setup_r, loop_r, eval_r = _main_parts(REF)
-    _, setup_o, loop_o, eval_o = _main_parts(OURS)
+    ref, ours = _reference_structure(), driver_structure(OURS)
     # (1) the training iteration
-    ev_r, ev_o = _events(loop_r.body, LOOP_CALLS), _events(loop_o.body, LOOP_CALLS)
+    ev_r, ev_o = ref["loop"], ours["loop"]
     assert ev_r == ev_o, "training iteration differs:\n ref  %s\n ours %s" % (ev_r, ev_o)
     names = [e[0] for e in ev_r]
     assert names == ["train", "autocast", "update_density_grid", "get_rays", "render", "mse_loss", "distortion_loss", "mean", "zero_grad",
                      "scale", "backward", "step", "update", "step"], names                      # what the comparison is about
     assert [e[3] for e in ev_r] == [False, False] + [True] * 6 + [False] * 6                      # inside autocast: grid update .. loss
     # (2) optimizer / scaler / scheduler construction
-    st_r, st_o = _events(setup_r, SETUP_CALLS), _events(setup_o, SETUP_CALLS)
+    st_r, st_o = ref["setup"], ours["setup"]
     assert st_r == st_o, "setup differs:\n ref  %s\n ours %s" % (st_r, st_o)
     assert [e[0] for e in st_r] == ["mark_invisible_cells", "GradScaler", "parameters", "FusedAdam", "parameters", "Adam", "CosineAnnealingLR"]
     # (3) the evaluation loop
-    ee_r, ee_o = _events([eval_r], EVAL_CALLS), _events([eval_o], EVAL_CALLS)
+    ee_r, ee_o = ref["eval"], ours["eval"]
     assert ee_r == ee_o, "evaluation loop differs:\n ref  %s\n ours %s" % (ee_r, ee_o)
-    assert ("render", 3, ("exp_step_factor", "test_time"), True) in ee_r
+    assert ["render", 3, ["exp_step_factor", "test_time"], True] in ee_r
     # (4) the loop bounds and the constants the protocol hangs on
-    src_r, src_o = ast.unparse(loop_r.iter), ast.unparse(loop_o.iter)
+    src_r, src_o = ref["loop_iter"], ours["loop_iter"]
     assert src_r == src_o == "range(hparams.max_steps + 1)"
-    for needle in ("warmup_steps = 256", "update_interval = 16", "exp_step_factor = 1 / 256 if hparams.scale > 0.5 else 0.0",
-                   "0.01 * MAX_SAMPLES / 3 ** 0.5", "step < warmup_steps", "step % update_interval == 0", "eps=1e-15", "hparams.lr / 30"):
-        for path in (REF, OURS):
-            assert needle in ast.unparse(ast.parse(open(path).read())), (needle, path)
+    assert ref["needles"] == ours["needles"] == list(NEEDLES)
 
 
 def test_example_is_not_a_copy_of_train_py():
-    """The example is written here: line-level similarity with the reference's driver stays far below what a copy would show."""
-    if not os.path.exists(REF):
-        pytest.skip("reference checkout not present")
-    import difflib
-    a = [x.strip() for x in open(REF).read().splitlines() if x.strip()]
-    b = [x.strip() for x in open(OURS).read().splitlines() if x.strip()]
-    assert difflib.SequenceMatcher(None, a, b).ratio() < 0.35
+    """The example is written here: line-level similarity with the reference's driver stays far below what a copy would show.  Measured
+    here where the checkout exists; elsewhere the ratio stored in tests/golden/ref_driver_shape.json is used, which holds for the
+    example file whose sha256 it records (after a change to the example, oracle/gen_golden_checkout.py re-measures it)."""
+    stored = json.load(open(DRIVER_SHAPE))["example_vs_train_py"]
+    if os.path.exists(REF):
+        now = example_similarity(REF)
+        if now["example_sha256"] == stored["example_sha256"]:
+            assert now == stored
+        ratio = now["line_similarity"]
+    else:
+        assert hashlib.sha256(open(OURS, "rb").read()).hexdigest() == stored["example_sha256"], (
+            "examples/train_reference_shape.py changed since its similarity with train.py was measured: run oracle/gen_golden_checkout.py "
+            "where the reference checkout exists")
+        ratio = stored["line_similarity"]
+    assert ratio < 0.35
 
 
 @pytest.mark.gpu
