@@ -171,6 +171,34 @@ int ngp_hash_fwd_list(const float* xyzs, const void* table, int table_kind, cons
 /* found_inf (nullable): set to 1 when a non-finite incoming gradient is seen -- GradScaler's inf/nan check
  * (train.py:199) done where the data passes instead of in an extra pass over the 45.7 MB gradient. */
 
+/* ---- a-4t  triplane_encoder_kernel fp32 + its autodiff backward (modules/triplane.py:35-98, glue :103-204) --------
+ * Level table of the tri-plane encoder (TriPlaneEncoder.__init__, triplane.py:103-160): the same f32 grid_scale / grid_resolution
+ * arithmetic as ngp_hash_levels (triplane.py:27-33), plus the full resolution every level's corners are mapped to.  Built on the
+ * host by ngp_triplane_levels_init and passed by pointer; the kernels copy what they need. */
+typedef struct ngp_triplane_levels {
+    int32_t  n_levels;                   /* L, <= NGP_MAX_LEVELS (the reference's NGP: 8)                        */
+    int32_t  n_features;                 /* F, features per entry (the reference's NGP: 4; the kernels take 4)   */
+    int32_t  max_res;                    /* side of each of the three planes, <= 16384                           */
+    int32_t  reserved;                   /* 0                                                                    */
+    float    scale[NGP_MAX_LEVELS];      /* base*exp(l*log_b)-1, f32                                             */
+    uint32_t resolution[NGP_MAX_LEVELS]; /* ceil(scale)+1                                                        */
+} ngp_triplane_levels;
+
+/* Host-only helper: fills `lv` like TriPlaneEncoder.__init__ (log_b = ln(max_res/base_res)/(L-1)). Returns 0, or -1 for bad arguments. */
+int ngp_triplane_levels_init(ngp_triplane_levels* lv, double base_res, double max_res, int levels, int features);
+/* Forward: replaces one launch of the reference's triplane_encoder_kernel (triplane.py:35-98, launched at :170).
+ * table = [3, max_res^2, F] f32 (planes (x,y), (y,z), (z,x)); out = [n, L*F] f32, FEATURE-major (column j*L + level).
+ * `normalize` fuses (x - lo) / (hi - lo) (networks.py:144) like ngp_hash_fwd_f32_ex; positions are then clamped to [0, 1]
+ * (the reference indexes out of bounds outside it).  Bit-exact to the reference's f32 arithmetic. */
+int ngp_triplane_fwd_f32(const float* xyzs /*[n,3]*/, const float* table, const ngp_triplane_levels* lv, int n, int normalize,
+                         float lo, float hi, float* out /*[n, L*F]*/, void* stream);
+/* Backward: replaces the Taichi-autodiff launch `_encode_kernel.grad` (triplane.py:186-198).  dtable += d out / d table for
+ * dout = d loss / d out: the TRUE gradient (the reference's glue returns the leaf's own .grad, which autograd adds a second time:
+ * 2x).  The gradient depends on the table values, which are read again here.  dtable must be zero-filled by the caller (or hold a
+ * gradient to accumulate into); float atomics: the summation order is not fixed. */
+int ngp_triplane_bwd_f32(const float* xyzs, const float* dout /*[n, L*F]*/, const float* table, const ngp_triplane_levels* lv,
+                         int n, int normalize, float lo, float hi, float* dtable, void* stream);
+
 /* ---- a-5  half2 encoder fwd / explicit bwd (modules/hash_encoder_half.py:112-161,164-213) ----
  * table/out/dout/dtable are IEEE binary16 pairs (uint16_t storage). */
 int ngp_hash_fwd_f16(const float* xyzs, const uint16_t* table, const ngp_hash_levels* lv, int n,

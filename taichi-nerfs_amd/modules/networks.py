@@ -88,20 +88,27 @@ class NGP(nn.Module):
         self.register_buffer('density_grid', torch.zeros(self.cascades, G3))
         self.register_buffer('grid_coords', _cell_coords(self.grid_size))
 
-        if pos_encoder_type != 'hash':
-            raise NotImplementedError("only the hash-grid position encoder is on the MI355X hot path "
-                                      "(the reference's tri-plane encoder is out of scope, see DESIGN.md)")
-        if half_opt:
-            from .hash_encoder_half import HashEncoder
-        else:
-            from .hash_encoder import HashEncoder
-        enc_kw = {}
-        if table_dtype is not None:                  # bf16 storage copy of the fp32 table (fp32 encoder only)
+        if pos_encoder_type == 'hash':
             if half_opt:
-                raise ValueError("table_dtype applies to the fp32 encoder; half_opt already selects the fp16 table")
-            enc_kw['table_dtype'] = table_dtype
-        self.pos_encoder = HashEncoder(max_params=2**log2_T, base_res=base_res, max_res=max_res, levels=levels,
-                                       feature_per_level=feature_per_level, **enc_kw)
+                from .hash_encoder_half import HashEncoder
+            else:
+                from .hash_encoder import HashEncoder
+            enc_kw = {}
+            if table_dtype is not None:                  # bf16 storage copy of the fp32 table (fp32 encoder only)
+                if half_opt:
+                    raise ValueError("table_dtype applies to the fp32 encoder; half_opt already selects the fp16 table")
+                enc_kw['table_dtype'] = table_dtype
+            self.pos_encoder = HashEncoder(max_params=2**log2_T, base_res=base_res, max_res=max_res, levels=levels,
+                                           feature_per_level=feature_per_level, **enc_kw)
+        elif pos_encoder_type == 'triplane':
+            # reference :101-107: base_res, levels and feature_per_level are fixed, half_opt does not apply (fp32 planes)
+            if table_dtype is not None:
+                raise ValueError("table_dtype applies to the hash encoder; the tri-plane table is fp32")
+            from .triplane import TriPlaneEncoder
+            self.pos_encoder = TriPlaneEncoder(base_res=16, max_res=max_res, levels=8, feature_per_level=4)
+        else:
+            raise NotImplementedError("pos_encoder_type must be 'hash' or 'triplane', got %r" % (pos_encoder_type,))
+        self.pos_encoder_type = pos_encoder_type
 
         self.xyz_encoder = MLP(input_dim=self.pos_encoder.out_dim, output_dim=xyz_net_out_dim, net_depth=xyz_net_depth,
                                net_width=xyz_net_width, bias_enabled=False)
@@ -121,8 +128,10 @@ class NGP(nn.Module):
 
     def fused_train_ok(self, rays):
         """Whole-render fusion (ngp_hip/fused.py): fp32 (or bf16-copy) hash table or the half2 encoder + default MLPs +
-        autocast(fp16) numerics."""
-        return (self._fused_ok(rays) and torch.is_grad_enabled() and os.environ.get("NGP_FUSED_RENDER", "1") != "0")
+        autocast(fp16) numerics.  The tri-plane encoder trains through march -> model(x, d) -> composite (its shading still runs the
+        fused MLP kernels)."""
+        return (self.pos_encoder_type == 'hash' and self._fused_ok(rays) and torch.is_grad_enabled()
+                and os.environ.get("NGP_FUSED_RENDER", "1") != "0")
 
     def _fused_ok(self, x):
         """Fused path = the fp16-autocast numerics of the reference's training/eval loops (train.py:177,250)."""

@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
 LIB_PATH = os.path.join(CSRC, "libngp_hip.so")
 SOURCES = ["march.hip", "hash_grid.hip", "hash_bwd_lds.hip", "composite.hip", "sh_grid.hip", "mlp.hip", "optim.hip", "distortion.hip", "occupancy.hip", "rays.hip",
-           "render.hip", "exchange.hip"]
+           "render.hip", "exchange.hip", "triplane.hip"]
 HEADERS = ["ngp_device.h", "hash_common.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 FLAGS_STAMP = LIB_PATH + ".flags"      # the flags the in-tree .so was built with: a flag change rebuilds
@@ -54,6 +54,18 @@ class HashLevels(ctypes.Structure):
 
 
 BWD_PLAN_DETERMINISTIC, BWD_PLAN_CONCENTRATED = 1, 2
+
+
+class TriPlaneLevels(ctypes.Structure):
+    """Mirror of `ngp_triplane_levels` (include/ngp_hip.h)."""
+    _fields_ = [
+        ("n_levels", ctypes.c_int32),
+        ("n_features", ctypes.c_int32),
+        ("max_res", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("scale", ctypes.c_float * NGP_MAX_LEVELS),
+        ("resolution", ctypes.c_uint32 * NGP_MAX_LEVELS),
+    ]
 
 
 def _render_fields():
@@ -125,6 +137,7 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int
 _F = ctypes.c_float
 _LV = ctypes.POINTER(HashLevels)
+_TLV = ctypes.POINTER(TriPlaneLevels)
 
 # name -> argtypes (restype is always int); must list every symbol include/ngp_hip.h and include/ngp_hip_experimental.h declare
 SIGNATURES = {
@@ -178,6 +191,9 @@ SIGNATURES = {
     "ngp_hash_bwd_sliced_main_adam": [_P, _LV, _I, _P, _I, _P, _P, ctypes.c_longlong, _P, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P],
     "ngp_hash_bwd_sliced_main_f16": [_P, _LV, _I, _P, _I, _P, _P, _P, ctypes.c_longlong, _P],
     "ngp_hash_bwd_f32_sliced": [_P, _P, _LV, _I, _P, _P, _I, _F, _F, _I, _P, _P, _P, ctypes.c_longlong, _P],
+    "ngp_triplane_levels_init": [_TLV, ctypes.c_double, ctypes.c_double, _I, _I],
+    "ngp_triplane_fwd_f32": [_P, _P, _TLV, _I, _I, _F, _F, _P, _P],
+    "ngp_triplane_bwd_f32": [_P, _P, _P, _TLV, _I, _I, _F, _F, _P, _P],
     "ngp_sh16_fwd": [_P, _I, _P, _P],
     "ngp_sh16_bwd": [_P, _P, _I, _P, _P],
     "ngp_composite_train_fwd": [_P, _P, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P],

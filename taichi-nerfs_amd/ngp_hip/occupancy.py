@@ -35,7 +35,8 @@ class OccupancyUpdater:
         self.stats = torch.zeros(self.L.ngp_occ_stats_floats(), **f32)        # [0] sum, [1] count, then the merge kernel's per-block partials
         self.wpack = torch.empty(self.L.ngp_mlp_wpack_halfs(), device=dev, dtype=torch.float16)
         lvs = getattr(getattr(model, "pos_encoder", None), "levels_struct", None)     # (None: a grid driven with density_fn only)
-        self.enc_pairs = 1 if (lvs is not None and lvs.n_levels == 16 and lvs.n_features == 2) else 0
+        self.triplane = getattr(model, "pos_encoder_type", "hash") == "triplane"      # plain column order: the module's own output
+        self.enc_pairs = 1 if (not self.triplane and lvs is not None and lvs.n_levels == 16 and lvs.n_features == 2) else 0
         self._su_work = self._su_out = None
 
     @torch.no_grad()
@@ -89,6 +90,9 @@ class OccupancyUpdater:
                 idx_ptr = _ptr(self.indices)
             if density_fn is not None:
                 self.sigmas[:n].copy_(density_fn(c, self.xyzs[:n], None if warmup else self.indices[:n]))
+            elif self.triplane:
+                check(L.ngp_triplane_fwd_f32(_ptr(self.xyzs), _ptr(m.pos_encoder.plane_embedding), ctypes.byref(lv), n, 1, lo, hi,
+                                             _ptr(self.enc), st), "ngp_triplane_fwd_f32")
             elif getattr(m, "half_opt", False):                                # half2 encoder: its own arithmetic on the f16 copy
                 check(L.ngp_hash_fwd_f16_ex(_ptr(self.xyzs), _ptr(m.pos_encoder.table_f16()), ctypes.byref(lv), n, _ptr(None), 1, lo, hi,
                                             self.enc_pairs, _ptr(self.enc), st), "ngp_hash_fwd_f16_ex")

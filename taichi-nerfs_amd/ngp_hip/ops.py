@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib_mod
-from .lib import HashLevels, check
+from .lib import HashLevels, TriPlaneLevels, check
 
 
 def _lib():
@@ -322,6 +322,44 @@ def hash_bwd_f16_sliced(xyzs, dout, lv, dtable_h, live_idx=None, n_dev=None):
                                          _stream()), "ngp_hash_bwd_sliced_main_f16")
     _touched(dtable_h)
     return dtable_h
+
+
+# ---------------------------------------------------------------------------------------------------- a-4t
+def make_triplane_levels(base_res, max_res, levels, features):
+    """ngp_triplane_levels table (host struct) -- TriPlaneEncoder.__init__ arithmetic (triplane.py:103-160)."""
+    lv = TriPlaneLevels()
+    check(_lib().ngp_triplane_levels_init(ctypes.byref(lv), float(base_res), float(max_res), int(levels), int(features)),
+          "ngp_triplane_levels_init")
+    return lv
+
+
+def _norm_args(xyz_min, xyz_max):
+    return (0, 0.0, 1.0) if xyz_min is None else (1, float(xyz_min), float(xyz_max))
+
+
+def triplane_fwd(xyzs, table, lv, xyz_min=None, xyz_max=None):
+    """[n,3] positions -> [n, L*F] f32, feature-major (column j*L + level).  Positions in [0,1] (clamped), or in [xyz_min, xyz_max]
+    when both are given (the (x - lo) / (hi - lo) of networks.py:144 is then done in the kernel)."""
+    _dev(xyzs, torch.float32, "xyzs"); _dev(table, torch.float32, "plane_embedding")
+    if table.numel() != 3 * lv.max_res**2 * lv.n_features:
+        raise ValueError("plane_embedding has %d floats, the level table needs %d" % (table.numel(), 3 * lv.max_res**2 * lv.n_features))
+    n = xyzs.shape[0]
+    out = torch.empty(n, lv.n_levels * lv.n_features, device=xyzs.device, dtype=torch.float32)
+    check(_lib().ngp_triplane_fwd_f32(_ptr(xyzs), _ptr(table), ctypes.byref(lv), n, *_norm_args(xyz_min, xyz_max), _ptr(out), _stream()),
+          "ngp_triplane_fwd_f32")
+    return out
+
+
+def triplane_bwd(xyzs, dout, table, lv, dtable, xyz_min=None, xyz_max=None):
+    """dtable += d(encoding)/d(table)^T dout: the true gradient of triplane_fwd (it depends on `table`)."""
+    _dev(xyzs, torch.float32, "xyzs"); _dev(dout, torch.float32, "dout"); _dev(table, torch.float32, "plane_embedding")
+    _dev(dtable, torch.float32, "dtable")
+    if dtable.numel() != table.numel() or dout.shape != (xyzs.shape[0], lv.n_levels * lv.n_features):
+        raise ValueError("triplane_bwd: dtable must match the table, dout must be [n, L*F]")
+    check(_lib().ngp_triplane_bwd_f32(_ptr(xyzs), _ptr(dout), _ptr(table), ctypes.byref(lv), xyzs.shape[0], *_norm_args(xyz_min, xyz_max),
+                                      _ptr(dtable), _stream()), "ngp_triplane_bwd_f32")
+    _touched(dtable)
+    return dtable
 
 
 # ---------------------------------------------------------------------------------------------------- a-6

@@ -54,6 +54,9 @@ class FusedTrainer:
                  growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, exp_step_factor=0.0, T_threshold=1e-4,
                  max_samples=1024, process_group=None, world_size=None, grad_comm_dtype=None,
                  distortion_loss_w=0.0, shard_optimizer=None, chunked_forward=None, exchange="rccl"):
+        if getattr(model, "pos_encoder_type", "hash") != "hash":
+            raise ValueError("FusedTrainer drives the hash-grid encoder only; train a %r model through the drop-in path "
+                             "(modules.rendering.render + a torch optimizer, as the reference's train.py does)" % model.pos_encoder_type)
         if not model.use_fused_mlp:
             raise ValueError("FusedTrainer needs the default architecture (L=16, F=2 hash grid, 64-wide MLPs)")
         self.half = bool(model.half_opt)              # half2 encoder (hash_encoder_half.py): f16 table copy, f16 gradient buffer
