@@ -199,6 +199,34 @@ int ngp_triplane_fwd_f32(const float* xyzs /*[n,3]*/, const float* table, const 
 int ngp_triplane_bwd_f32(const float* xyzs, const float* dout /*[n, L*F]*/, const float* table, const ngp_triplane_levels* lv,
                          int n, int normalize, float lo, float hi, float* dtable, void* stream);
 
+/* ---- a-4v  VoxelGrid.forward / query_grids + sh_utils.eval_sh and their backward (modules/networks.py:382-575, sh_utils.py:58-113)
+ * The reference's svox model never ran (its forward names undefined variables); these entry points are the lookup its helpers
+ * describe: normalize_samples (:521-522), query_grids(use_trilinear=False) (:546-559) with out_of_grid (:491-508), eval_sh of degree
+ * 0-4 per colour channel (:572-574), and the PlenOctrees activations sigma = relu(density), rgb = sigmoid(SH) (voxel grid).
+ * sh = [G, G, G, 3*D] f32 with D = (sh_degree+1)^2, channel-major (R's D coefficients, then G's, then B's); density = [G, G, G] f32;
+ * (x, y, z) 'ij' order.  Sample p reads row (ix*G + iy)*G + iz, i = rint((p - grid_min) / grid_radius) per axis (f32, IEEE divide,
+ * half-to-even like torch.round); an axis outside [0, G) gives the all-zero row: sigma = 0, rgb = sigmoid(0) = 0.5, no gradient.
+ * grid_min = f32(1 - ceil(G/2)) * f32(grid_radius) (grid_normalized_coords.min(0), :470-478).  G <= 1024, 64-bit row offsets. */
+int ngp_voxel_fwd(const float* xyzs /*[n,3]*/, const float* dirs /*[n,3], any length*/, const float* sh, const float* density, int n,
+                  int grid_size, int sh_degree, float grid_min, float grid_radius, float* sigmas /*[n]*/, float* rgbs /*[n,3]*/,
+                  void* stream);
+/* Density only (the occupancy update's query, networks.py:255-290 on VoxelGrid.density). */
+int ngp_voxel_density(const float* xyzs, const float* density, int n, int grid_size, float grid_min, float grid_radius,
+                      float* sigmas, void* stream);
+/* Backward of ngp_voxel_fwd: dsh += d loss / d sh, ddensity += d loss / d density, from the saved sigmas / rgbs (the relu passes the
+ * gradient where sigma > 0, the sigmoid's derivative is rgb (1 - rgb)); the row is recomputed from xyzs, the field is not read.
+ * dsh / ddensity must be zero-filled by the caller (or hold a gradient to accumulate into); float atomics: the order is not fixed. */
+int ngp_voxel_bwd(const float* xyzs, const float* dirs, const float* sigmas, const float* rgbs, const float* dsigmas /*[n]*/,
+                  const float* drgbs /*[n,3]*/, int n, int grid_size, int sh_degree, float grid_min, float grid_radius, float* dsh,
+                  float* ddensity, void* stream);
+/* packbits (utils.py:157-169) of VoxelGrid.update_density_grid: bit = density >= threshold and density > 0, threshold =
+ * min(mean of the positive cells, density_threshold), the mean summed in f64 in a fixed order.  NGP's packbits (`>` against an f32
+ * mean) marks none or all cells of a fresh grid that holds one value everywhere, depending on how the mean rounds.
+ * scratch: ngp_voxel_occ_scratch_doubles() doubles; n_bytes = cells / 8. */
+int ngp_voxel_occ_scratch_doubles(void);
+int ngp_voxel_occ_pack(const float* density_grid, long long n_bytes, double density_threshold, double* scratch, uint8_t* bitfield,
+                       void* stream);
+
 /* ---- a-5  half2 encoder fwd / explicit bwd (modules/hash_encoder_half.py:112-161,164-213) ----
  * table/out/dout/dtable are IEEE binary16 pairs (uint16_t storage). */
 int ngp_hash_fwd_f16(const float* xyzs, const uint16_t* table, const ngp_hash_levels* lv, int n,

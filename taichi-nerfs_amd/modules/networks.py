@@ -66,6 +66,27 @@ def _cell_coords(grid_size):
     return torch.stack(torch.meshgrid(r, r, r, indexing='ij'), dim=-1).reshape(-1, 3)
 
 
+def _merge_fresh_densities(model, density_threshold, warmup, decay, erode, jitter):
+    """The torch formulation of the occupancy update up to the threshold (reference networks.py:255-284): a jittered point in every
+    cell (warm-up) or in M = G^3/4 uniform + M occupied cells, model.density there, then density_grid = max(decay * grid, fresh)
+    where the cell is visible."""
+    fresh = torch.zeros_like(model.density_grid)
+    cells = model.get_all_cells() if warmup else \
+        model.sample_uniform_and_occupied_cells(model.grid_size**3 // 4, density_threshold)
+    for c in range(model.cascades):
+        indices, coords = cells[c]
+        s = min(2**(c - 1), model.scale)
+        half_grid = s / model.grid_size
+        xyzs_w = (coords / (model.grid_size - 1) * 2 - 1) * (s - half_grid)
+        u = torch.rand_like(xyzs_w) if jitter is None else jitter(c, len(indices)).to(xyzs_w)   # (all cells: Morton-sorted rows)
+        xyzs_w += (u * 2 - 1) * half_grid                                # random point inside the cell
+        fresh[c, indices] = model.density(xyzs_w).float()
+    if erode:
+        decay = torch.clamp(decay**(1 / model.count_grid), 0.1, 0.95)
+    model.density_grid = torch.where(model.density_grid < 0, model.density_grid,
+                                     torch.maximum(model.density_grid * decay, fresh))
+
+
 class NGP(nn.Module):
 
     def __init__(self, scale: float = 0.5, pos_encoder_type: str = 'hash', levels: int = 16, feature_per_level: int = 2,
@@ -231,21 +252,7 @@ class NGP(nn.Module):
             if not self.density_grid.is_contiguous():
                 self.density_grid = self.density_grid.contiguous()
             return upd.update(density_threshold, warmup=warmup, decay=decay, jitter=jitter)
-        fresh = torch.zeros_like(self.density_grid)
-        cells = self.get_all_cells() if warmup else \
-            self.sample_uniform_and_occupied_cells(self.grid_size**3 // 4, density_threshold)
-        for c in range(self.cascades):
-            indices, coords = cells[c]
-            s = min(2**(c - 1), self.scale)
-            half_grid = s / self.grid_size
-            xyzs_w = (coords / (self.grid_size - 1) * 2 - 1) * (s - half_grid)
-            u = torch.rand_like(xyzs_w) if jitter is None else jitter(c, len(indices)).to(xyzs_w)   # (all cells: Morton-sorted rows)
-            xyzs_w += (u * 2 - 1) * half_grid                                # random point inside the cell
-            fresh[c, indices] = self.density(xyzs_w).float()
-        if erode:
-            decay = torch.clamp(decay**(1 / self.count_grid), 0.1, 0.95)
-        self.density_grid = torch.where(self.density_grid < 0, self.density_grid,
-                                        torch.maximum(self.density_grid * decay, fresh))
+        _merge_fresh_densities(self, density_threshold, warmup, decay, erode, jitter)
         mean_density = self.density_grid[self.density_grid > 0].mean().item()
         packbits(self.density_grid.reshape(-1).contiguous(), min(mean_density, density_threshold), self.density_bitfield)
 
@@ -303,13 +310,119 @@ class MLP(nn.Module):
         return x
 
 
-class VoxelGrid(nn.Module):
-    """Placeholder so `from modules.networks import NGP, VoxelGrid, MODEL_DICT` (reference train.py:18) resolves.
-    The reference's svox model is unfinished upstream (undefined names in its forward) and out of scope."""
+class _VoxelShade(torch.autograd.Function):
+    """ngp_voxel_fwd / ngp_voxel_bwd: nearest-voxel lookup, relu density, sigmoid(eval_sh) colour; the backward adds into freshly
+    zeroed dense gradients of both fields."""
 
-    def __init__(self, *args, **kwargs):
+    @staticmethod
+    def forward(ctx, x, d, sh_fields, density_fields, cfg):
+        sigmas, rgbs = _ops.voxel_fwd(x, d, sh_fields, density_fields, *cfg)
+        ctx.save_for_backward(x, d, sigmas, rgbs)
+        ctx.cfg = cfg
+        ctx.shapes = (sh_fields.shape, density_fields.shape)
+        ctx.set_materialize_grads(False)
+        return sigmas, rgbs
+
+    @staticmethod
+    def backward(ctx, g_sigmas, g_rgbs):
+        x, d, sigmas, rgbs = ctx.saved_tensors
+        G, deg, m, r = ctx.cfg
+        g_sigmas = torch.zeros_like(sigmas) if g_sigmas is None else g_sigmas.contiguous().float()
+        g_rgbs = torch.zeros_like(rgbs) if g_rgbs is None else g_rgbs.contiguous().float()
+        dsh = torch.zeros(ctx.shapes[0], device=x.device, dtype=torch.float32)
+        ddensity = torch.zeros(ctx.shapes[1], device=x.device, dtype=torch.float32)
+        _ops.voxel_bwd(x, d, sigmas, rgbs, g_sigmas, g_rgbs, G, deg, m, r, dsh, ddensity)
+        return None, None, dsh, ddensity, None
+
+
+class VoxelGrid(nn.Module):
+    """Explicit voxel-grid radiance field of reference modules/networks.py:382-575 (`--model_name svox`), finished.
+
+    Upstream's model never ran: its forward names undefined variables, its concatenated `grid_fields` is a copy the optimizer never
+    reaches, and `super().__init__()` builds an unused NGP hash encoder and MLPs.  So no upstream svox checkpoint exists, and this
+    class carries neither NGP's encoder nor its MLPs: the state_dict holds `sh_fields` [G,G,G,3*D], `density_fields` [G,G,G,1] and
+    the occupancy buffers.  The lookup is the one the reference's helpers describe (normalize_samples, query_grids with
+    use_trilinear=False, out_of_grid) with PlenOctrees' activations: sigma = relu(density), rgb = sigmoid(eval_sh(deg, sh_c, d/|d|))
+    per channel (channel-major coefficients).  Both directions are the HIP kernels ngp_voxel_fwd / ngp_voxel_bwd (voxel
+    grid).  `half_opt` is accepted and ignored (upstream: "available for hash")."""
+
+    def __init__(self, scale: float = 0.5, half_opt: bool = False, sh_degree: int = 2, grid_size: int = 256,
+                 grid_radius: float = 0.0125, origin_sh: float = 0., origin_sigma: float = 0.1):
         super().__init__()
-        raise NotImplementedError("model_name='svox' is not part of the MI355X hot path")
+        if not isinstance(sh_degree, (int, np.integer)) or not 0 <= sh_degree <= 4:
+            raise ValueError("sh_degree must be 0-4 (sh_utils.eval_sh), got %r" % (sh_degree,))
+        G = grid_size
+        if not isinstance(G, (int, np.integer)) or G < 16 or G > 512 or G & (G - 1):
+            raise ValueError("grid_size must be a power of two in [16, 512] (Morton-addressed occupancy bitfield), got %r" % (G,))
+        D = (sh_degree + 1)**2
+        if G**3 * 3 * D >= 2**31:
+            raise ValueError("sh_fields of %d^3 x %d floats is too large (>= 2^31 elements)" % (G, 3 * D))
+        if not grid_radius > 0:
+            raise ValueError("grid_radius must be positive, got %r" % (grid_radius,))
+        self.scale = scale
+        self.half_opt = bool(half_opt)
+        self.sh_degree = int(sh_degree)
+        self.grid_size = int(G)
+        self.grid_radius = grid_radius
+        self.origin_sh = origin_sh
+        self.origin_sigma = origin_sigma
+        self.sh_dim = D
+        self.register_buffer('center', torch.zeros(1, 3))
+        self.register_buffer('xyz_min', -torch.ones(1, 3) * scale)
+        self.register_buffer('xyz_max', torch.ones(1, 3) * scale)
+        self.register_buffer('half_size', (self.xyz_max - self.xyz_min) / 2)
+        self.cascades = max(1 + int(np.ceil(np.log2(2 * scale))), 1)
+        G3 = G**3
+        self.register_buffer('density_bitfield', torch.zeros(self.cascades * G3 // 8, dtype=torch.uint8))
+        self.register_buffer('density_grid', torch.zeros(self.cascades, G3))
+        self.register_buffer('grid_coords', _cell_coords(G))
+        # initialize_grid (:436-487): grid point (i, j, k) sits at ((i, j, k) - ceil(G/2) + 1) * grid_radius
+        self.sh_fields = nn.Parameter(torch.full((G, G, G, 3 * D), float(origin_sh), dtype=torch.float32))
+        self.density_fields = nn.Parameter(torch.full((G, G, G, 1), float(origin_sigma), dtype=torch.float32))
+        # grid_normalized_coords.min(0) as torch forms it: f32 index times f32 radius
+        self.grid_min = float(np.float32(1 - np.ceil(G / 2)) * np.float32(grid_radius))
+        self.render_func = VolumeRenderer()
+        self._occ_scratch = None
+
+    def fused_train_ok(self, rays):
+        """No whole-render fusion: render() takes march -> model(x, d) -> composite for this model."""
+        return False
+
+    def _cfg(self):
+        return (self.grid_size, self.sh_degree, self.grid_min, float(self.grid_radius))
+
+    # ------------------------------------------------------------------------------------------ shading
+    def forward(self, x, d):
+        """x: [N,3] positions, d: [N,3] directions (any length) -> (sigmas [N], rgbs [N,3]), fp32 with or without autocast."""
+        return _VoxelShade.apply(x.contiguous().float(), d.contiguous().float(), self.sh_fields, self.density_fields, self._cfg())
+
+    def density(self, x):
+        """x: [N,3] -> sigmas [N] (differentiable w.r.t. density_fields when grad mode is on)."""
+        x = x.contiguous().float()
+        if torch.is_grad_enabled() and self.density_fields.requires_grad:
+            return self.forward(x, torch.ones_like(x))[0]
+        return _ops.voxel_density(x, self.density_fields, self.grid_size, self.grid_min, float(self.grid_radius))
+
+    # ------------------------------------------------------------------------------------------ occupancy grid
+    get_all_cells = NGP.get_all_cells
+    sample_uniform_and_occupied_cells = NGP.sample_uniform_and_occupied_cells
+    mark_invisible_cells = NGP.mark_invisible_cells
+
+    @torch.no_grad()
+    def update_density_grid(self, density_threshold, warmup=False, decay=0.95, erode=False, jitter=None):
+        """NGP's update (:255-290) on VoxelGrid.density, with one change at the threshold: the mean is summed in f64 and a cell is
+        occupied when its density is >= min(mean, density_threshold) (and positive).  A fresh field holds origin_sigma in every
+        visible cell; with NGP's strict `>` against an f32 mean the first warm-up marks all of them or none, depending on how the
+        mean rounds, and with none nothing ever trains."""
+        if jitter is not None and not warmup:
+            raise ValueError("an explicit jitter is defined for the warm-up form (all cells) only")
+        _merge_fresh_densities(self, density_threshold, warmup, decay, erode, jitter)
+        if not self.density_grid.is_contiguous():
+            self.density_grid = self.density_grid.contiguous()
+        if self._occ_scratch is None or self._occ_scratch.device != self.density_grid.device:
+            self._occ_scratch = torch.empty(_ops._lib().ngp_voxel_occ_scratch_doubles(), device=self.density_grid.device,
+                                            dtype=torch.float64)
+        _ops.voxel_occ_pack(self.density_grid, density_threshold, self.density_bitfield, self._occ_scratch)
 
 
 MODEL_DICT = {'ngp': NGP, 'svox': VoxelGrid}

@@ -362,6 +362,76 @@ def triplane_bwd(xyzs, dout, table, lv, dtable, xyz_min=None, xyz_max=None):
     return dtable
 
 
+# ---------------------------------------------------------------------------------------------------- a-4v
+def _voxel_fields(sh, density, grid_size, sh_degree):
+    _dev(sh, torch.float32, "sh_fields"); _dev(density, torch.float32, "density_fields")
+    G, D = int(grid_size), (int(sh_degree) + 1)**2
+    if sh.numel() != G**3 * 3 * D or density.numel() != G**3:
+        raise ValueError("voxel fields must be [G,G,G,3*D] and [G,G,G,1] for G=%d, degree %d" % (G, sh_degree))
+
+
+def voxel_fwd(xyzs, dirs, sh, density, grid_size, sh_degree, grid_min, grid_radius):
+    """positions [n,3], directions [n,3] -> (sigmas [n], rgbs [n,3]): nearest voxel of (p - grid_min) / grid_radius, relu density,
+    sigmoid of eval_sh per channel (VoxelGrid, modules/networks.py)."""
+    _dev(xyzs, torch.float32, "xyzs"); _dev(dirs, torch.float32, "dirs")
+    _voxel_fields(sh, density, grid_size, sh_degree)
+    n = xyzs.shape[0]
+    if xyzs.shape != (n, 3) or dirs.shape != (n, 3):
+        raise ValueError("voxel_fwd: xyzs and dirs must both be [n, 3], got %s and %s" % (tuple(xyzs.shape), tuple(dirs.shape)))
+    sigmas = torch.empty(n, device=xyzs.device, dtype=torch.float32)
+    rgbs = torch.empty(n, 3, device=xyzs.device, dtype=torch.float32)
+    check(_lib().ngp_voxel_fwd(_ptr(xyzs), _ptr(dirs), _ptr(sh), _ptr(density), n, int(grid_size), int(sh_degree), float(grid_min),
+                               float(grid_radius), _ptr(sigmas), _ptr(rgbs), _stream()), "ngp_voxel_fwd")
+    return sigmas, rgbs
+
+
+def voxel_density(xyzs, density, grid_size, grid_min, grid_radius, out=None):
+    _dev(xyzs, torch.float32, "xyzs"); _dev(density, torch.float32, "density_fields")
+    if density.numel() != int(grid_size)**3:
+        raise ValueError("density_fields must hold G^3 values")
+    n = xyzs.shape[0]
+    if xyzs.shape != (n, 3) or (out is not None and (out.shape != (n,) or not out.is_contiguous() or out.dtype != torch.float32)):
+        raise ValueError("voxel_density: xyzs must be [n, 3] and out a contiguous f32 [n]")
+    sigmas = torch.empty(n, device=xyzs.device, dtype=torch.float32) if out is None else out
+    check(_lib().ngp_voxel_density(_ptr(xyzs), _ptr(density), n, int(grid_size), float(grid_min), float(grid_radius), _ptr(sigmas),
+                                   _stream()), "ngp_voxel_density")
+    return sigmas
+
+
+def voxel_bwd(xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, grid_size, sh_degree, grid_min, grid_radius, dsh, ddensity):
+    """dsh += d loss / d sh_fields, ddensity += d loss / d density_fields (both zero-filled by the caller)."""
+    for t, name in ((xyzs, "xyzs"), (dirs, "dirs"), (sigmas, "sigmas"), (rgbs, "rgbs"), (dsigmas, "dsigmas"), (drgbs, "drgbs")):
+        _dev(t, torch.float32, name)
+    _voxel_fields(dsh, ddensity, grid_size, sh_degree)
+    n = xyzs.shape[0]
+    if dirs.shape != (n, 3) or sigmas.shape != (n,) or rgbs.shape != (n, 3) or dsigmas.shape != (n,) or drgbs.shape != (n, 3):
+        raise ValueError("voxel_bwd: per-sample tensors must be [n], [n,3]")
+    check(_lib().ngp_voxel_bwd(_ptr(xyzs), _ptr(dirs), _ptr(sigmas), _ptr(rgbs), _ptr(dsigmas), _ptr(drgbs), n, int(grid_size),
+                               int(sh_degree), float(grid_min), float(grid_radius), _ptr(dsh), _ptr(ddensity), _stream()), "ngp_voxel_bwd")
+    _touched(dsh, ddensity)
+    return dsh, ddensity
+
+
+def voxel_occ_pack(density_grid, density_threshold, density_bitfield, scratch=None):
+    """bit = density >= min(f64 mean of the positive cells, density_threshold) and density > 0 (VoxelGrid.update_density_grid).
+    The kernel reads density_grid as float4: it must start on a 16-byte boundary (a fresh torch allocation does)."""
+    _dev(density_grid, torch.float32, "density_grid"); _dev(density_bitfield, torch.uint8, "density_bitfield")
+    n_bytes = density_bitfield.numel()
+    if density_grid.numel() != 8 * n_bytes:
+        raise ValueError("density_grid must hold 8 cells per bitfield byte")
+    if density_grid.data_ptr() % 16:
+        raise ValueError("density_grid must start on a 16-byte boundary (the packing kernel reads float4)")
+    if scratch is not None and (scratch.dtype != torch.float64 or not scratch.is_cuda
+                                or scratch.numel() < _lib().ngp_voxel_occ_scratch_doubles()):
+        raise ValueError("scratch must be a device f64 buffer of ngp_voxel_occ_scratch_doubles() values")
+    if scratch is None:
+        scratch = torch.empty(_lib().ngp_voxel_occ_scratch_doubles(), device=density_grid.device, dtype=torch.float64)
+    check(_lib().ngp_voxel_occ_pack(_ptr(density_grid), n_bytes, float(density_threshold), _ptr(scratch), _ptr(density_bitfield),
+                                    _stream()), "ngp_voxel_occ_pack")
+    _touched(density_bitfield)
+    return density_bitfield
+
+
 # ---------------------------------------------------------------------------------------------------- a-6
 def sh16_fwd(dirs):
     _dev(dirs, torch.float32, "dirs")

@@ -54,6 +54,9 @@ class FusedTrainer:
                  growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, exp_step_factor=0.0, T_threshold=1e-4,
                  max_samples=1024, process_group=None, world_size=None, grad_comm_dtype=None,
                  distortion_loss_w=0.0, shard_optimizer=None, chunked_forward=None, exchange="rccl"):
+        if not hasattr(model, "pos_encoder"):
+            raise ValueError("FusedTrainer drives NGP's hash-grid encoder only; train a %s through the drop-in path "
+                             "(modules.rendering.render + a torch optimizer, as the reference's train.py does)" % type(model).__name__)
         if getattr(model, "pos_encoder_type", "hash") != "hash":
             raise ValueError("FusedTrainer drives the hash-grid encoder only; train a %r model through the drop-in path "
                              "(modules.rendering.render + a torch optimizer, as the reference's train.py does)" % model.pos_encoder_type)
