@@ -583,6 +583,17 @@ int ngp_occ_merge(float* density_grid, const float* tmp, float decay, int n, flo
 int ngp_occ_pack(const float* density_grid, float* stats, float density_threshold, int n_bytes, uint8_t* bitfield,
                  void* stream);
 
+/* ---- deployment model (train.py --deployment; csrc/deploy.hip) --------------------------------------------------------------------
+ * Shading of the exported 4-level, 4-feature dense grid with 16-wide MLPs, all fp32, one launch: xyzs [n,3] world positions in
+ * [-0.5, 0.5] (x01 = xyz + 0.5), dirs [n,3] of any length.  table: the fp32 hash table [total_entries, 4], 16-byte aligned; lv: the
+ * level table of ngp_hash_levels_init(2^21, 4, 32, 128, 4) (4 levels, 4 features, every level dense: anything else is -1).
+ * sigma_w [512] = W1 [16][16] | W2 [16][16], rgb_w [768] = W3 [16][32] | W4 [16][16] whose first 3 rows are the colour rows, both
+ * row-major [out][in] as save_deployment_model writes them.  sigma = exp(W2 relu(W1 enc))[0], rgb = sigmoid(W4 relu(W3 [SH16 | 16])).
+ * The dense index is taken modulo the level's entry count like the training encoder, so no position reads out of bounds.
+ * enc_out (nullable, [n,16], 16-byte aligned): the embedding, bit-identical to ngp_hash_fwd_f32 on x01 (tests only). */
+int ngp_deploy_shade(const float* xyzs, const float* dirs, const float* table, const ngp_hash_levels* lv, const float* sigma_w,
+                     const float* rgb_w, int n, float* sigmas /*[n]*/, float* rgbs /*[n,3]*/, float* enc_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -432,6 +432,29 @@ def voxel_occ_pack(density_grid, density_threshold, density_bitfield, scratch=No
     return density_bitfield
 
 
+# ---------------------------------------------------------------------------------------------------- a-4d
+def deploy_shade(xyzs, dirs, table, lv, sigma_w, rgb_w, return_enc=False):
+    """The deployment model's shading in one launch (ngp_deploy_shade): world positions [n,3] in [-0.5, 0.5] and directions [n,3]
+    -> (sigmas [n], rgbs [n,3]) f32, plus the [n,16] embedding with return_enc=True (tests).  table: fp32 [entries * 4] of the level
+    table `lv` = make_levels(2**21, 4, 32, 128, 4); sigma_w [512], rgb_w [768] in save_deployment_model's layout."""
+    for t, name in ((xyzs, "xyzs"), (dirs, "dirs"), (table, "hash_table"), (sigma_w, "sigma_weights"), (rgb_w, "rgb_weights")):
+        _dev(t, torch.float32, name)
+    n = xyzs.shape[0]
+    if xyzs.shape != (n, 3) or dirs.shape != (n, 3):
+        raise ValueError("deploy_shade: xyzs and dirs must both be [n, 3], got %s and %s" % (tuple(xyzs.shape), tuple(dirs.shape)))
+    if lv.n_levels != 4 or lv.n_features != 4 or lv.begin_fast_hash_level != 4:
+        raise ValueError("deploy_shade needs the deployment level table: 4 dense levels of 4 features")
+    if table.numel() != lv.total_entries * 4 or sigma_w.numel() != 512 or rgb_w.numel() != 768:
+        raise ValueError("deploy_shade: table must hold %d floats, sigma_weights 512, rgb_weights 768 (got %d, %d, %d)"
+                         % (lv.total_entries * 4, table.numel(), sigma_w.numel(), rgb_w.numel()))
+    sigmas = torch.empty(n, device=xyzs.device, dtype=torch.float32)
+    rgbs = torch.empty(n, 3, device=xyzs.device, dtype=torch.float32)
+    enc = torch.empty(n, 16, device=xyzs.device, dtype=torch.float32) if return_enc else None
+    check(_lib().ngp_deploy_shade(_ptr(xyzs), _ptr(dirs), _ptr(table), ctypes.byref(lv), _ptr(sigma_w), _ptr(rgb_w), n, _ptr(sigmas),
+                                  _ptr(rgbs), _ptr(enc), _stream()), "ngp_deploy_shade")
+    return (sigmas, rgbs, enc) if return_enc else (sigmas, rgbs)
+
+
 # ---------------------------------------------------------------------------------------------------- a-6
 def sh16_fwd(dirs):
     _dev(dirs, torch.float32, "dirs")
