@@ -3,8 +3,8 @@
 // Replaces, for inference from an exported model, hash_encode + sigma_rgb_layer of the reference's
 // deployment/InstantNGP/taichi_ngp/kernels.py (:385-445, :449-518) with ONE launch: world position + direction in, (sigma, rgb) out.
 //   x01 = xyz + 0.5; 4 dense levels x 8 corners, one 16-byte gather per corner (4 features), trilinear weights and the
-//   mul-then-add accumulation of hash_grid.hip's `corners` / hash_fwd_f32_kernel<4> (bit-identical embedding);
-//   d / |d| -> (d + 1) / 2 -> the 16 SH terms of kernels.py:141-173, in that file's operation order;
+//   mul-then-add accumulation of hash_fwd_f32_kernel<4>, through the same corner rule (hash_common.h: bit-identical embedding);
+//   d / |d| -> (d + 1) / 2 -> the 16 SH terms of kernels.py:141-173, in that file's operation order (sh16_quad, ngp_device.h);
 //   16 -> 16 (ReLU) -> 16, sigma = exp(out[0]);  [SH16 | 16] -> 16 (ReLU) -> 3, sigmoid; every sum runs over its inputs in index
 //   order, as the reference's loops do.  All arithmetic is fp32.  The embedding and the SH terms are separate multiplies and adds
 //   (the library is built with -ffp-contract=off; the embedding is checked bit for bit); the 1280 multiply-adds of the two networks
@@ -25,6 +25,7 @@
 // only per-sample memory traffic besides 24 B in and 16 B out: 32 gathers x 16 B = 512 B per sample.  175 VGPRs, no scratch: two
 // waves per SIMD.
 #include "ngp_device.h"
+#include "hash_common.h"
 
 namespace ngp {
 
@@ -36,23 +37,11 @@ struct DeployLevels {
 __device__ __forceinline__ void deploy_sh16(float dx, float dy, float dz, float* __restrict__ sh) {
     const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
     const float x = (dx / nrm + 1.0f) / 2.0f, y = (dy / nrm + 1.0f) / 2.0f, z = (dz / nrm + 1.0f) / 2.0f;
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    sh[0] = 0.28209479177387814f;
-    sh[1] = -0.48860251190291987f * y;
-    sh[2] = 0.48860251190291987f * z;
-    sh[3] = -0.48860251190291987f * x;
-    sh[4] = 1.0925484305920792f * xy;
-    sh[5] = -1.0925484305920792f * yz;
-    sh[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-    sh[7] = -1.0925484305920792f * xz;
-    sh[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    sh[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-    sh[10] = 2.8906114426405538f * xy * z;
-    sh[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    sh[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-    sh[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-    sh[14] = 1.4453057213202769f * z * (x2 - y2);
-    sh[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
+    const float4 q[4] = {sh16_quad<0>(x, y, z), sh16_quad<1>(x, y, z), sh16_quad<2>(x, y, z), sh16_quad<3>(x, y, z)};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        sh[4 * g] = q[g].x; sh[4 * g + 1] = q[g].y; sh[4 * g + 2] = q[g].z; sh[4 * g + 3] = q[g].w;
+    }
 }
 
 __global__ void __launch_bounds__(256) deploy_shade_kernel(const float* __restrict__ xyzs, const float* __restrict__ dirs,
@@ -66,37 +55,28 @@ __global__ void __launch_bounds__(256) deploy_shade_kernel(const float* __restri
         const float px = xyzs[3 * (size_t)i] + 0.5f, py = xyzs[3 * (size_t)i + 1] + 0.5f, pz = xyzs[3 * (size_t)i + 2] + 0.5f;
         const float dx = dirs[3 * (size_t)i], dy = dirs[3 * (size_t)i + 1], dz = dirs[3 * (size_t)i + 2];
 
-        // ---- embedding: 4 levels x 8 corners (hash_grid.hip `corners<false>` on a dense level, F = 4)
+        // ---- embedding: 4 levels x 8 corners (the corner rule of hash_common.h on a dense level, F = 4)
         float in[32];                               // [SH16 | geometry feature]; the embedding lives in `enc` until the first layer is done
         float enc[16];
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-            const float scale = lv.scale[l];
             const uint32_t res = lv.res[l], size = lv.size[l], res2 = res * res;
-            const float pos[3] = {px * scale + 0.5f, py * scale + 0.5f, pz * scale + 0.5f};
+            const float p[3] = {px, py, pz};
             uint32_t cell[3];
             float fr[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                cell[k] = f2u_sat(floorf(pos[k]));
-                fr[k] = pos[k] - (float)cell[k];
-            }
+            cell_frac<false>(p, lv.scale[l], cell, fr);
             const float4* lt = reinterpret_cast<const float4*>(table) + lv.offset[l];
             float4 v[8];
             float w[8];
 #pragma unroll
             for (int ci = 0; ci < 8; ++ci) {
-                float wc = 1.0f;
-                uint32_t g[3];
-#pragma unroll
-                for (int d = 0; d < 3; ++d) {
-                    if ((ci & (1 << d)) == 0) { g[d] = cell[d]; wc *= 1.0f - fr[d]; }
-                    else { g[d] = cell[d] + 1u; wc *= fr[d]; }
-                }
-                uint32_t h = g[0] + g[1] * res + g[2] * res2;
-                if (h >= size) h %= size;            // the training encoder's `% map_size`: always < size, whatever the position
+                // the training encoder's dense index `% map_size`: level_index(dense, mode 0) without the subtract in front of
+                // the modulo (one branch per corner instead of two in a kernel at 175 VGPRs) -- the same value for every
+                // input, always < size, whatever the position and whatever table the caller hands over
+                uint32_t h = (cell[0] + (ci & 1)) + (cell[1] + ((ci >> 1) & 1)) * res + (cell[2] + (ci >> 2)) * res2;
+                if (h >= size) h %= size;
                 v[ci] = lt[h];
-                w[ci] = wc;
+                w[ci] = corner_weight(ci, fr);
             }
             float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
 #pragma unroll

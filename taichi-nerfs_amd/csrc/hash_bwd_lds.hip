@@ -52,8 +52,6 @@
 // inside each wave's gather -> weights -> adds chain.
 #include "ngp_device.h"
 #include "hash_common.h"
-#include <stdlib.h>
-#include <string.h>
 
 namespace ngp {
 
@@ -79,17 +77,8 @@ struct BwdPlan {
     uint16_t xoff[8], xlen[8];
 };
 
-__device__ __forceinline__ uint32_t level_index(bool dense, uint32_t mode, uint32_t size, uint32_t res, uint32_t gx, uint32_t gy,
-                                                uint32_t gz) {
-    uint32_t h = dense ? (gx + gy * res + gz * res * res) : (gx ^ (gy * 2654435761u) ^ (gz * 805459861u));   // :53-60 / :43-51
-    if (mode == 1u) h &= (size - 1u);
-    else if (mode == 0u) { if (h >= size) { h -= size; if (h >= size) h %= size; } }
-    else h = h % size;                                                                                       // :71
-    return h;
-}
-
 // dense level whose table holds the whole grid (mode 0: size >= res^3, so x + y res + z res^2 < 2 size and `% size` is one
-// conditional subtract): the eight corner indices from one base index, branch-free
+// conditional subtract): the eight corner indices from one base index, branch-free.  Equals level_index(dense, mode 0) there.
 __device__ __forceinline__ uint32_t dense0_index(uint32_t base, uint32_t res, uint32_t res2, uint32_t size, int c) {
     uint32_t h = base + (uint32_t)(c & 1) + (((c >> 1) & 1) ? res : 0u) + ((c >> 2) ? res2 : 0u);
     return h >= size ? h - size : h;
@@ -134,7 +123,7 @@ __host__ __device__ __forceinline__ SliceMap slice_map(uint32_t size, uint32_t r
 // instructions, profiles/r04_pmc.json).
 struct PrepLevel {
     float scale;
-    uint32_t res, size, mode;        // mode as load_levels derives it: 0 dense (conditional subtract), 1 hashed pow2 (mask), 2 real modulo
+    uint32_t res, size, mode;        // level_mode
     SliceMap map;
 };
 struct PrepLevels { PrepLevel l[NGP_MAX_LEVELS]; };
@@ -143,17 +132,10 @@ static PrepLevels make_prep_levels(const ngp_hash_levels& lv) {
     for (int t = 0; t < lv.n_levels && t < NGP_MAX_LEVELS; ++t) {
         PrepLevel& q = P.l[t];
         q.scale = lv.scale[t]; q.res = lv.resolution[t]; q.size = lv.map_size[t];
-        const bool dense = t < lv.begin_fast_hash_level;
-        if (dense) { const uint64_t r = q.res; q.mode = ((uint64_t)q.size >= r * r * r && r >= 2) ? 0u : 2u; }
-        else q.mode = (q.size != 0 && (q.size & (q.size - 1)) == 0) ? 1u : 2u;
-        q.map = slice_map(q.size, q.res, dense);
+        q.mode = level_mode(lv, t);
+        q.map = slice_map(q.size, q.res, t < lv.begin_fast_hash_level);
     }
     return P;
-}
-
-__device__ __forceinline__ const float* grad_ptr(const float* dout, int level, size_t i, size_t plane, int enc_pairs, int nl) {
-    return enc_pairs ? dout + ((size_t)(level < 8 ? level : 15 - level) * plane + i) * 4 + (level < 8 ? 0 : 2)
-                     : dout + i * (size_t)(nl * 2) + level * 2;
 }
 
 // ---- prepass: compact positions, per-(level, slice) hit bitmaps -------------------------------------------------------------
@@ -200,8 +182,7 @@ __global__ void __launch_bounds__(256) hash_bwd_prep_kernel(const float* __restr
             if ((single_slice_levels >> level) & 1u) continue;             // every sample is a hit there: no bitmap needed
             const PrepLevel& P = pl.l[level];
             const uint32_t res = P.res, size = P.size, mode = P.mode;
-            const uint32_t cx = f2u_sat(floorf(x * P.scale + 0.5f)), cy = f2u_sat(floorf(y * P.scale + 0.5f)),
-                           cz = f2u_sat(floorf(z * P.scale + 0.5f));
+            const uint32_t cx = level_cell(x, P.scale), cy = level_cell(y, P.scale), cz = level_cell(z, P.scale);
             const bool dense = level < bfhl;
             const SliceMap SM = P.map;
             unsigned long long* row = bitmap + ((size_t)level * BW_MAX_SLICES) * wstride + tile;
@@ -231,14 +212,14 @@ __global__ void __launch_bounds__(256) hash_bwd_prep_kernel(const float* __restr
                 for (int level = lb; level < le; ++level) {
                     const PrepLevel& P = pl.l[level];
                     const uint32_t res = P.res, size = P.size, mode = P.mode;
-                    const uint32_t cx = f2u_sat(floorf(x * P.scale + 0.5f)), cy = f2u_sat(floorf(y * P.scale + 0.5f)),
-                                   cz = f2u_sat(floorf(z * P.scale + 0.5f));
+                    const uint32_t cx = level_cell(x, P.scale), cy = level_cell(y, P.scale), cz = level_cell(z, P.scale);
                     const bool dense = level < bfhl;
                     const SliceMap SM = P.map;
                     unsigned long long* wd = words[wave][level - lb];
                     if (!dense && mode == 1u && res < (1u << BW_SLICE_LOG2)) {
                         // xor hash, power-of-two table: x only flips bits below the slice bits -> one slice per (y, z) combination
-                        const uint32_t b0 = cy * 2654435761u, b1 = b0 + 2654435761u, c0 = cz * 805459861u, c1 = c0 + 805459861u;
+                        // (level_index(hashed, mode 1) with (g + 1) * prime = g * prime + prime mod 2^32)
+                        const uint32_t b0 = cy * HASH_PRIME_Y, b1 = b0 + HASH_PRIME_Y, c0 = cz * HASH_PRIME_Z, c1 = c0 + HASH_PRIME_Z;
                         const uint32_t msk = size - 1u;
                         atomicOr(&wd[((b0 ^ c0) & msk) >> BW_SLICE_LOG2], 1ull << lane);         // ds_or_b64
                         atomicOr(&wd[((b1 ^ c0) & msk) >> BW_SLICE_LOG2], 1ull << lane);
@@ -296,11 +277,9 @@ struct __attribute__((packed, aligned(4))) F3 {
     float x, y, z;
 };
 
-__device__ __forceinline__ float round16(float v) { return f16_round(v); }      // through fp16 (RNE) and back, never fused into the product
-
 __device__ __forceinline__ Hit load_hit(const int level, const int i, const bool valid, const float* __restrict__ xyzc,
                                         const float* __restrict__ dout, const size_t plane, const int enc_pairs, const int nl,
-                                        int32_t* __restrict__ found_inf, const uint32_t diag = 0u, const bool half = false) {
+                                        const uint32_t diag = 0u, const bool half = false) {
     Hit h = {0.f, 0.f, 0.f, 0.f, 0.f};
 #ifdef NGP_BWD_DIAG
     if (diag & 2u) { const float t = (float)(i & 1023) * (1.0f / 1024.0f); h.x = t; h.y = 1.0f - t; h.z = 0.5f * t; h.g0 = 1.0f; h.g1 = t; return h; }
@@ -311,9 +290,9 @@ __device__ __forceinline__ Hit load_hit(const int level, const int i, const bool
 #ifdef NGP_BWD_DIAG
         if (diag & 8u) { h.g0 = 1.0f; h.g1 = 0.5f; return h; }      // timing experiment: ONE gather per hit (no gradient load)
 #endif
-        const float2 g = *reinterpret_cast<const float2*>(grad_ptr(dout, level, (size_t)i, plane, enc_pairs, nl));
+        const float2 g = *reinterpret_cast<const float2*>(enc_ptr(dout, level, (size_t)i, plane, enc_pairs, nl));
         h.g0 = g.x; h.g1 = g.y;
-        if (half) { h.g0 = round16(h.g0); h.g1 = round16(h.g1); }      // half2 encoder: its output gradient is an fp16 tensor
+        if (half) { h.g0 = f16_round(h.g0); h.g1 = f16_round(h.g1); }      // half2 encoder: its output gradient is an fp16 tensor
     }
     return h;
 }
@@ -354,37 +333,38 @@ enum { KIND_GENERIC = 0, KIND_HASHED = 1, KIND_MERGE = 2, KIND_MERGE0 = 3,      
 
 // One batch of <= 64 hits (one per lane): accumulate this level's contributions that fall into slice `sl`.
 template <int KIND>
-__device__ __forceinline__ void accumulate(const LevelParams P, const uint32_t sl, const bool single, const Hit H, const bool valid,
+__device__ __forceinline__ void accumulate(const LevelParams P, const uint32_t sl, const Hit H, const bool valid,
                                            double* __restrict__ slice) {
     constexpr bool HALF = (KIND & KIND_HALF) != 0;
     constexpr int K = KIND & 3;
     const int lane = threadIdx.x & 63;
     float g0 = H.g0, g1 = H.g1;
-    const float px = H.x * P.scale + 0.5f, py = H.y * P.scale + 0.5f, pz = H.z * P.scale + 0.5f;
-    uint32_t cx = f2u_sat(floorf(px)), cy = f2u_sat(floorf(py)), cz = f2u_sat(floorf(pz));
-    const float fx = px - (HALF ? round16((float)cx) : (float)cx), fy = py - (HALF ? round16((float)cy) : (float)cy),
-                fz = pz - (HALF ? round16((float)cz) : (float)cz);
-    auto R = [](float v) { return HALF ? round16(v) : v; };
+    const float p[3] = {H.x, H.y, H.z};
+    uint32_t cell[3];
+    float fr[3];
+    cell_frac<HALF>(p, P.scale, cell, fr);
+    uint32_t cx = cell[0];
+    const uint32_t cy = cell[1], cz = cell[2];
+    auto R = [](float v) { return HALF ? f16_round(v) : v; };
     const bool act = valid && (g0 != 0.0f || g1 != 0.0f);           // exact-zero gradients contribute nothing
     if (K == KIND_HASHED) {
         // xor hash into a power-of-two table with res < 2^13: h = (gx ^ A) & mask, A = gy P1 ^ gz P2; gx < 2^13 cannot reach the
         // slice bits, so both x corners of a (y, z) combination share the slice, and two multiplies serve all four combinations
+        // (level_index(hashed, mode 1) with (g + 1) * prime = g * prime + prime mod 2^32)
         const uint32_t msk = P.size - 1u;
-        const uint32_t b0 = cy * 2654435761u, b1 = b0 + 2654435761u, c0 = cz * 805459861u, c1 = c0 + 805459861u;
+        const uint32_t b0 = cy * HASH_PRIME_Y, b1 = b0 + HASH_PRIME_Y, c0 = cz * HASH_PRIME_Z, c1 = c0 + HASH_PRIME_Z;
         const uint32_t A0 = b0 ^ c0, A1 = b1 ^ c0, A2 = b0 ^ c1, A3 = b1 ^ c1;             // k = (z bit, y bit)
         uint32_t m = 0u;
         if (act) {
             m = (uint32_t)(((A0 & msk) >> BW_SLICE_LOG2) == sl) | ((uint32_t)(((A1 & msk) >> BW_SLICE_LOG2) == sl) << 1) |
                 ((uint32_t)(((A2 & msk) >> BW_SLICE_LOG2) == sl) << 2) | ((uint32_t)(((A3 & msk) >> BW_SLICE_LOG2) == sl) << 3);
         }
-        const float wx0 = 1.0f * (1.0f - fx), wx1 = 1.0f * fx;                               // same product order as the forward
         while (__any(m != 0u)) {
             if (m != 0u) {
                 const int k = __builtin_ctz(m);
                 m &= m - 1u;
                 const uint32_t A = (k & 2) ? ((k & 1) ? A3 : A2) : ((k & 1) ? A1 : A0);
-                const float wy = (k & 1) ? fy : 1.0f - fy, wz = (k & 2) ? fz : 1.0f - fz;
-                const float w0 = (wx0 * wy) * wz, w1 = (wx1 * wy) * wz;
+                const float w0 = corner_weight(2 * k, fr), w1 = corner_weight(2 * k + 1, fr);
                 double* p0 = slice + 2 * (((cx ^ A) & msk) & (BW_SLICE_ENTRIES - 1));
                 double* p1 = slice + 2 * ((((cx + 1u) ^ A) & msk) & (BW_SLICE_ENTRIES - 1));
                 LDS_ADD(p0, R(w0 * g0)); LDS_ADD(p0 + 1, R(w0 * g1));
@@ -398,13 +378,12 @@ __device__ __forceinline__ void accumulate(const LevelParams P, const uint32_t s
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                               // k = (z bit, y bit)
                 const int yb = k & 1, zb = k >> 1;
-                const float wyz_y = yb ? fy : 1.0f - fy, wyz_z = zb ? fz : 1.0f - fz;
 #pragma unroll
                 for (int xb = 0; xb < 2; ++xb) {
                     uint32_t loc;
                     const uint32_t h = level_index(P.dense, P.mode, P.size, P.res, cx + xb, cy + yb, cz + zb);
                     if (slice_of(P.map, h, loc) == sl) {
-                        const float w = ((1.0f * (xb ? fx : 1.0f - fx)) * wyz_y) * wyz_z;
+                        const float w = corner_weight(2 * k + xb, fr);
                         double* p = slice + 2 * loc;
                         LDS_ADD(p, R(w * g0));
                         LDS_ADD(p + 1, R(w * g1));
@@ -422,7 +401,7 @@ __device__ __forceinline__ void accumulate(const LevelParams P, const uint32_t s
     float v0[8], v1[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const float w = ((1.0f * ((c & 1) ? fx : 1.0f - fx)) * (((c >> 1) & 1) ? fy : 1.0f - fy)) * ((c >> 2) ? fz : 1.0f - fz);
+        const float w = corner_weight(c, fr);
         v0[c] = R(w * g0); v1[c] = R(w * g1);
     }
     const uint32_t pcx = (uint32_t)row_shr_i<1>((int)cx, -1), pcy = (uint32_t)row_shr_i<1>((int)cy, -1), pcz = (uint32_t)row_shr_i<1>((int)cz, -1);
@@ -455,17 +434,16 @@ struct Batch {
 
 __device__ __forceinline__ Batch load_batch(const int level, const int i0, const bool v0, const int i1, const bool v1,
                                             const float* __restrict__ xyzc, const float* __restrict__ dout, const size_t plane,
-                                            const int enc_pairs, const int nl, int32_t* __restrict__ found_inf, const uint32_t diag,
-                                            const bool half) {
+                                            const int enc_pairs, const int nl, const uint32_t diag, const bool half) {
     Batch b;
     b.v0 = v0; b.v1 = v1;
-    b.h0 = load_hit(level, i0, v0, xyzc, dout, plane, enc_pairs, nl, found_inf, diag, half);
-    b.h1 = load_hit(level, i1, v1, xyzc, dout, plane, enc_pairs, nl, found_inf, diag, half);
+    b.h0 = load_hit(level, i0, v0, xyzc, dout, plane, enc_pairs, nl, diag, half);
+    b.h1 = load_hit(level, i1, v1, xyzc, dout, plane, enc_pairs, nl, diag, half);
     return b;
 }
 
 template <int KIND>
-__device__ __forceinline__ void accumulate_batch(const LevelParams P, const uint32_t sl, const bool single, const Batch& b,
+__device__ __forceinline__ void accumulate_batch(const LevelParams P, const uint32_t sl, const Batch& b,
                                                  double* __restrict__ slice, int32_t* __restrict__ found_inf) {
     // GradScaler's inf/nan check, where the data passes -- here, not at the load: testing a value the moment it is requested
     // would make the wave wait for the gather it has just issued
@@ -473,8 +451,8 @@ __device__ __forceinline__ void accumulate_batch(const LevelParams P, const uint
 #ifdef NGP_BWD_DIAG
     if (P.diag & 4u) { asm volatile("" :: "v"(b.h0.x), "v"(b.h0.g0), "v"(b.h1.x), "v"(b.h1.g0)); return; }
 #endif
-    accumulate<KIND>(P, sl, single, b.h0, b.v0, slice);
-    accumulate<KIND>(P, sl, single, b.h1, b.v1, slice);
+    accumulate<KIND>(P, sl, b.h0, b.v0, slice);
+    accumulate<KIND>(P, sl, b.h1, b.v1, slice);
 }
 
 // One task: software-pipelined.  The wave's share of the hit bitmap is fetched 64 words (4096 samples) per vector load, one
@@ -500,11 +478,11 @@ __device__ __forceinline__ void bwd_task(const LevelParams P, const int level, c
     if (single) {
         for (int w0 = lo_w + 2 * wave; w0 < hi_w; w0 += 2 * BW_WAVES) {
             const int i0 = w0 * 64 + lane, i1 = i0 + 64;
-            const Batch nxt = load_batch(level, i0, i0 < n, i1, (w0 + 1 < hi_w) && i1 < n, xyzc, dout, plane, enc_pairs, nl, found_inf, P.diag, HALF);
-            accumulate_batch<KIND>(P, sl, true, pend, slice, found_inf);
+            const Batch nxt = load_batch(level, i0, i0 < n, i1, (w0 + 1 < hi_w) && i1 < n, xyzc, dout, plane, enc_pairs, nl, P.diag, HALF);
+            accumulate_batch<KIND>(P, sl, pend, slice, found_inf);
             pend = nxt;
         }
-        accumulate_batch<KIND>(P, sl, true, pend, slice, found_inf);
+        accumulate_batch<KIND>(P, sl, pend, slice, found_inf);
         return;
     }
     int qhead = 0, qlen = 0;
@@ -534,8 +512,8 @@ __device__ __forceinline__ void bwd_task(const LevelParams P, const int level, c
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         __builtin_amdgcn_wave_barrier();
         const int i0 = (int)q[(qhead + lane) & (BW_Q - 1)], i1 = (int)q[(qhead + 64 + lane) & (BW_Q - 1)];
-        const Batch nxt = load_batch(level, i0, true, i1, true, xyzc, dout, plane, enc_pairs, nl, found_inf, P.diag, HALF);
-        accumulate_batch<KIND>(P, sl, false, pend, slice, found_inf);
+        const Batch nxt = load_batch(level, i0, true, i1, true, xyzc, dout, plane, enc_pairs, nl, P.diag, HALF);
+        accumulate_batch<KIND>(P, sl, pend, slice, found_inf);
         pend = nxt;
         __builtin_amdgcn_wave_barrier();
         qhead = (qhead + 128) & (BW_Q - 1); qlen -= 128;
@@ -618,8 +596,8 @@ __device__ __forceinline__ void bwd_task(const LevelParams P, const int level, c
             __builtin_amdgcn_wave_barrier();
             const bool v0 = lane < qlen, v1 = lane + 64 < qlen;
             const int i0 = v0 ? (int)q[(qhead + lane) & (BW_Q - 1)] : 0, i1 = v1 ? (int)q[(qhead + 64 + lane) & (BW_Q - 1)] : 0;
-            const Batch nxt = load_batch(level, i0, v0, i1, v1, xyzc, dout, plane, enc_pairs, nl, found_inf, P.diag, HALF);
-            accumulate_batch<KIND>(P, sl, false, pend, slice, found_inf);
+            const Batch nxt = load_batch(level, i0, v0, i1, v1, xyzc, dout, plane, enc_pairs, nl, P.diag, HALF);
+            accumulate_batch<KIND>(P, sl, pend, slice, found_inf);
             pend = nxt;
             __builtin_amdgcn_wave_barrier();
             qhead = (qhead + 128) & (BW_Q - 1); qlen = 0;
@@ -631,11 +609,11 @@ __device__ __forceinline__ void bwd_task(const LevelParams P, const int level, c
         __builtin_amdgcn_wave_barrier();
         const bool v0 = lane < qlen, v1 = lane + 64 < qlen;
         const int i0 = v0 ? (int)q[(qhead + lane) & (BW_Q - 1)] : 0, i1 = v1 ? (int)q[(qhead + 64 + lane) & (BW_Q - 1)] : 0;
-        const Batch nxt = load_batch(level, i0, v0, i1, v1, xyzc, dout, plane, enc_pairs, nl, found_inf, P.diag, HALF);
-        accumulate_batch<KIND>(P, sl, false, pend, slice, found_inf);
+        const Batch nxt = load_batch(level, i0, v0, i1, v1, xyzc, dout, plane, enc_pairs, nl, P.diag, HALF);
+        accumulate_batch<KIND>(P, sl, pend, slice, found_inf);
         pend = nxt;
     }
-    accumulate_batch<KIND>(P, sl, false, pend, slice, found_inf);
+    accumulate_batch<KIND>(P, sl, pend, slice, found_inf);
 }
 
 // Queue heads: ctr[x] = tasks taken from the front of XCD x's queue (low 16 bits, by its own workgroups) and from the back (high
@@ -788,8 +766,7 @@ __global__ void __launch_bounds__(BW_THREADS) hash_bwd_lds_kernel(const float* _
     LevelParams P;
     P.scale = lv.scale[level]; P.res = lv.resolution[level]; P.size = lv.map_size[level]; P.offset = lv.offset[level];
     P.dense = level < lv.begin_fast_hash_level;
-    if (P.dense) { const uint64_t r = P.res; P.mode = ((uint64_t)P.size >= r * r * r && r >= 2) ? 0u : 2u; }
-    else P.mode = (P.size != 0 && (P.size & (P.size - 1)) == 0) ? 1u : 2u;
+    P.mode = level_mode(lv, level);
     P.map = slice_map(P.size, P.res, P.dense);
     P.diag = plan.diag;
     P.det = plan.det;
@@ -836,8 +813,7 @@ __global__ void __launch_bounds__(BW_THREADS) hash_bwd_lds_kernel(const float* _
     } else if (ADAM && nrep == 1) {
         // the optimizer in the flush (see FlushAdam): UNR entries per thread and trip with all their loads in flight
         const bool skip = ad.si[SI_SKIP] != 0;
-        const float inv_scale = ad.sf[SF_INV_SCALE], step_size = ad.sf[SF_LR] / ad.sf[SF_BC1], bc2_sqrt = ad.sf[SF_BC2_SQRT];
-        const float beta1 = ad.beta1, beta2 = ad.beta2, eps = ad.eps;
+        const AdamConsts ac = adam_consts(ad.sf, ad.beta1, ad.beta2, ad.eps);
         float2* p2 = reinterpret_cast<float2*>(ad.p) + P.offset;
         float2* m2 = reinterpret_cast<float2*>(ad.m) + P.offset;
         float2* v2 = reinterpret_cast<float2*>(ad.v) + P.offset;
@@ -878,16 +854,8 @@ __global__ void __launch_bounds__(BW_THREADS) hash_bwd_lds_kernel(const float* _
                 // step is skipped and the loss scale backs off (the two-launch path would have skipped THIS step: same scale trajectory
                 // one step later, no poisoned parameter).
                 if (!(isfinite(gx) && isfinite(gy))) { atomicOr(&ctr[9], 1u); continue; }
-#define NGP_ADAM1(c, g)                                                       \
-                {                                                             \
-                    const float gr = (g) * inv_scale;                         \
-                    mk.c = mk.c + (gr - mk.c) * (1.0f - beta1);               \
-                    vk.c = vk.c * beta2 + gr * gr * (1.0f - beta2);           \
-                    const float denom = sqrtf(vk.c) / bc2_sqrt + eps;         \
-                    pk.c = pk.c - step_size * (mk.c / denom);                 \
-                }
-                NGP_ADAM1(x, gx) NGP_ADAM1(y, gy)
-#undef NGP_ADAM1
+                adam_update(pk.x, mk.x, vk.x, gx, ac);
+                adam_update(pk.y, mk.y, vk.y, gy, ac);
                 p2[h[k]] = pk; m2[h[k]] = mk; v2[h[k]] = vk;
                 if (ADAM == 2) sh[h[k]] = f32_to_bf16_bits(pk.x) | (f32_to_bf16_bits(pk.y) << 16);
             }

@@ -28,46 +28,28 @@ struct Corners {
 // hash_encoder.py:100-137; HALF_CELL applies hash_encoder_half.py:133 (cell cast to f16 before the subtract)
 template <bool HALF_CELL>
 __device__ __forceinline__ void corners(const LevelLDS& L, int level, int bfhl, float x, float y, float z, Corners& c) {
-    const float scale = L.scale[level];
     const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level];
-    float pos[3] = {x * scale + 0.5f, y * scale + 0.5f, z * scale + 0.5f};
+    const float p[3] = {x, y, z};
     uint32_t cell[3];
     float fr[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        cell[k] = f2u_sat(floorf(pos[k]));
-        float cf = (float)cell[k];
-        if (HALF_CELL) cf = __half2float(__float2half_rn(cf));
-        fr[k] = pos[k] - cf;
-    }
+    cell_frac<HALF_CELL>(p, L.scale[level], cell, fr);
     const bool dense = level < bfhl;
-    const uint32_t res2 = res * res;
 #pragma unroll
     for (int ci = 0; ci < 8; ++ci) {
-        float w = 1.0f;
-        uint32_t g[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if ((ci & (1 << d)) == 0) { g[d] = cell[d]; w *= 1.0f - fr[d]; }
-            else { g[d] = cell[d] + 1u; w *= fr[d]; }
-        }
-        uint32_t h = dense ? (g[0] + g[1] * res + g[2] * res2)                     // under_hash :53-60
-                           : (g[0] ^ (g[1] * 2654435761u) ^ (g[2] * 805459861u));  // fast_hash :43-51
-        if (mode == 1u) h &= (size - 1u);
-        else if (mode == 0u) { if (h >= size) { h -= size; if (h >= size) h %= size; } }
-        else h = h % size;
-        c.idx[ci] = L.offset[level] + h;
-        c.w[ci] = w;
+        c.idx[ci] = L.offset[level] + level_index(dense, mode, size, res, cell[0] + (ci & 1), cell[1] + ((ci >> 1) & 1), cell[2] + (ci >> 2));
+        c.w[ci] = corner_weight(ci, fr);
     }
 }
 
 // The same corners for ONE level whose constants the caller holds in registers, without a branch: both index forms are one
 // three-operand instruction per corner (v_add3 / v_xor3) behind per-axis terms ((c + 1) * k = c * k + k mod 2^32), and `% size` is
 // `& (size - 1)` on a power-of-two hashed level or one conditional subtract (min(h, h - size), unsigned) on a dense one -- exactly
-// `corners` above, but with c.idx RELATIVE to the level's first entry (the caller folds the offset into its base pointer); a lane
-// whose level needs the real modulo (mode 2, or a dense index >= 2 * size) reports it in the return value and the caller redoes
-// that lane's eight indices with `%` under ONE rarely taken branch.  Straight-line code keeps the
-// eight gathers of an iteration -- and the next iteration's position request -- in one basic block.
+// `corners` above (level_index modes 0 and 1), but with c.idx RELATIVE to the level's first entry (the caller folds the offset
+// into its base pointer); a lane whose level needs the real modulo (mode 2, or a dense index >= 2 * size) reports it in the
+// return value and the caller redoes that lane's eight indices with `%` under ONE rarely taken branch.  Straight-line code keeps
+// the eight gathers of an iteration -- and the next iteration's position request -- in one basic block.
+// The weight is corner_weight(ci, fr) (hash_common.h), kept as the in-place product loop: through the call the compiler
+// schedules the gather loop differently, and this loop's instruction stream is what the gather's timing rests on.
 struct LevelRegs {
     float scale;
     uint32_t res, size, mode, offset;
@@ -82,17 +64,11 @@ struct LevelRegs {
 };
 template <bool HALF_CELL>
 __device__ __forceinline__ bool corners_flat(const LevelRegs& lr, float x, float y, float z, Corners& c, uint32_t h_raw[8]) {
-    float pos[3] = {x * lr.scale + 0.5f, y * lr.scale + 0.5f, z * lr.scale + 0.5f};
+    const float p[3] = {x, y, z};
     uint32_t cell[3];
     float fr[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        cell[k] = f2u_sat(floorf(pos[k]));
-        float cf = (float)cell[k];
-        if (HALF_CELL) cf = __half2float(__float2half_rn(cf));
-        fr[k] = pos[k] - cf;
-    }
-    const uint32_t ky = lr.dense ? lr.res : 2654435761u, kz = lr.dense ? lr.res * lr.res : 805459861u;
+    cell_frac<HALF_CELL>(p, lr.scale, cell, fr);
+    const uint32_t ky = lr.dense ? lr.res : HASH_PRIME_Y, kz = lr.dense ? lr.res * lr.res : HASH_PRIME_Z;
     const uint32_t ax[2] = {cell[0], cell[0] + 1u};
     const uint32_t ay[2] = {cell[1] * ky, cell[1] * ky + ky};
     const uint32_t az[2] = {cell[2] * kz, cell[2] * kz + kz};
@@ -101,7 +77,7 @@ __device__ __forceinline__ bool corners_flat(const LevelRegs& lr, float x, float
     for (int ci = 0; ci < 8; ++ci) {
         float w = 1.0f;
 #pragma unroll
-        for (int d = 0; d < 3; ++d) w *= (ci & (1 << d)) ? fr[d] : 1.0f - fr[d];
+        for (int d = 0; d < 3; ++d) w *= (ci & (1 << d)) ? fr[d] : 1.0f - fr[d];   // = corner_weight(ci, fr)
         const uint32_t gx = ax[ci & 1], gy = ay[(ci >> 1) & 1], gz = az[(ci >> 2) & 1];
         const uint32_t h = lr.dense ? gx + gy + gz : gx ^ gy ^ gz;                 // under_hash :53-60 / fast_hash :43-51
         h_raw[ci] = h;
@@ -230,6 +206,7 @@ __global__ void __launch_bounds__(256) hash_fwd_f32_xcd_kernel(const float* __re
         }
         return make_float2(a0, a1);
     };
+    // = enc_ptr(out, level, i, plane, enc_pairs, 16), from the pair / which this block and lane already hold
     auto out_at = [&](int i) { return reinterpret_cast<float2*>(enc_pairs ? out + ((size_t)pair * plane + i) * 4 + which * 2 : out + (size_t)i * 32 + level * 2); };
     if constexpr (V1) {
         for (int i = (blockIdx.x >> 3) * 128 + (threadIdx.x >> 1); i < n; i += tiles * 128) {
@@ -283,7 +260,7 @@ __global__ void __launch_bounds__(256) hash_fwd_f32_xcd_kernel(const float* __re
             uint32_t h_raw[8];
             if (corners_flat<MODE == 2>(lr, xyz[0], xyz[1], xyz[2], c, h_raw)) {
 #pragma unroll
-                for (int ci = 0; ci < 8; ++ci) c.idx[ci] = h_raw[ci] % lr.size;
+                for (int ci = 0; ci < 8; ++ci) c.idx[ci] = h_raw[ci] % lr.size;              // level_index mode 2
             }
 #ifdef NGP_HASH_FWD_DIAG
             // timing experiment (profiles/microbench/encoder_ab.py NGP_EXPERIMENT hash_fwd_free_levels): the gathers of the levels in the mask
@@ -370,37 +347,27 @@ __global__ void __launch_bounds__(256) hash_bwd_f32x2_kernel(const float* __rest
             x = norm01(nm, xyzs[3 * src]); y = norm01(nm, xyzs[3 * src + 1]); z = norm01(nm, xyzs[3 * src + 2]);
         }
         for (int level = 0; level < nl; ++level) {
-            const size_t gi = enc_pairs ? ((size_t)(level < 8 ? level : 15 - level) * plane + i) * 4 + (level < 8 ? 0 : 2) + f
-                                        : (size_t)i * (nl * 2) + level * 2 + f;
-            const float g = valid ? dout[gi] : 0.0f;
+            const float g = valid ? enc_ptr(dout, level, (size_t)i, plane, enc_pairs, nl)[f] : 0.0f;
             if (found_inf && !isfinite(g)) *found_inf = 1;          // GradScaler's inf/nan check, done where the data passes
-            const float scale = L.scale[level];
             const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level];
-            const float px = x * scale + 0.5f, py = y * scale + 0.5f, pz = z * scale + 0.5f;
-            const uint32_t cx = f2u_sat(floorf(px)), cy = f2u_sat(floorf(py)), cz = f2u_sat(floorf(pz));
-            const float fx = px - (float)cx, fy = py - (float)cy, fz = pz - (float)cz;
+            const float p[3] = {x, y, z};
+            uint32_t cell[3];
+            float fr[3];
+            cell_frac<false>(p, L.scale[level], cell, fr);
+            const uint32_t cx = cell[0], cy = cell[1], cz = cell[2];
             // run structure: head = first sample of the tile or a different cell than the previous sample
             const uint32_t pcx = __shfl_up(cx, 4, 64), pcy = __shfl_up(cy, 4, 64), pcz = __shfl_up(cz, 4, 64);
             const int pvalid = __shfl_up((int)valid, 4, 64);
             bool head = (s_in == 0) || !valid || !pvalid || cx != pcx || cy != pcy || cz != pcz;
             const int nhead = __shfl_down((int)head, 4, 64);
             const bool tail = valid && ((s_in == 15) || nhead);
-            const float wx = xb ? fx : 1.0f - fx;
-            const uint32_t gx = cx + (uint32_t)xb;
             float v[4];
             uint32_t e[4];
             const bool dense = level < bfhl;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {              // k = (z bit, y bit)
-                const int yb = k & 1, zb = k >> 1;
-                const float w = (1.0f * wx) * (yb ? fy : 1.0f - fy) * (zb ? fz : 1.0f - fz);   // same product order as fwd
-                const uint32_t gy = cy + (uint32_t)yb, gz = cz + (uint32_t)zb;
-                uint32_t h = dense ? (gx + gy * res + gz * res * res) : (gx ^ (gy * 2654435761u) ^ (gz * 805459861u));
-                if (mode == 1u) h &= (size - 1u);
-                else if (mode == 0u) { if (h >= size) { h -= size; if (h >= size) h %= size; } }
-                else h = h % size;
-                e[k] = L.offset[level] + h;
-                v[k] = w * g;
+                e[k] = L.offset[level] + level_index(dense, mode, size, res, cx + (uint32_t)xb, cy + (uint32_t)(k & 1), cz + (uint32_t)(k >> 1));
+                v[k] = corner_weight(2 * k + xb, fr) * g;
             }
             // segmented inclusive scan over samples (lane distance 4 = one sample)
             bool hf = head;
@@ -509,40 +476,27 @@ __global__ void __launch_bounds__(256) hash_bwd_f16x2_kernel(const float* __rest
         }
         for (int level = 0; level < nl; ++level) {
             float2 g = make_float2(0.f, 0.f);
-            if (valid) {
-                const float* gp = enc_pairs ? dout + ((size_t)(level < 8 ? level : 15 - level) * plane + i) * 4 + (level < 8 ? 0 : 2)
-                                            : dout + (size_t)i * (nl * 2) + level * 2;
-                g = *reinterpret_cast<const float2*>(gp);
-            }
+            if (valid) g = *reinterpret_cast<const float2*>(enc_ptr(dout, level, (size_t)i, plane, enc_pairs, nl));
             g = __half22float2(__floats2half2_rn(g.x, g.y));              // the encoder's output gradient is an fp16 tensor
             if (found_inf && !(isfinite(g.x) && isfinite(g.y))) *found_inf = 1;
-            const float scale = L.scale[level];
             const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level];
-            const float px = x * scale + 0.5f, py = y * scale + 0.5f, pz = z * scale + 0.5f;
-            const uint32_t cx = f2u_sat(floorf(px)), cy = f2u_sat(floorf(py)), cz = f2u_sat(floorf(pz));
-            // hash_encoder_half.py:133: the cell is cast to f16 before the subtract
-            const float fx = px - __half2float(__float2half_rn((float)cx)), fy = py - __half2float(__float2half_rn((float)cy)),
-                        fz = pz - __half2float(__float2half_rn((float)cz));
+            const float p[3] = {x, y, z};
+            uint32_t cell[3];
+            float fr[3];
+            cell_frac<true>(p, L.scale[level], cell, fr);
+            const uint32_t cx = cell[0], cy = cell[1], cz = cell[2];
             const uint32_t pcx = __shfl_up(cx, 2, 64), pcy = __shfl_up(cy, 2, 64), pcz = __shfl_up(cz, 2, 64);
             const int pvalid = __shfl_up((int)valid, 2, 64);
             const bool head = (s_in == 0) || !valid || !pvalid || cx != pcx || cy != pcy || cz != pcz;
             const int nhead = __shfl_down((int)head, 2, 64);
             const bool tail = valid && ((s_in == 31) || nhead);
-            const float wx = xb ? fx : 1.0f - fx;
-            const uint32_t gx = cx + (uint32_t)xb;
             float v0[4], v1[4];
             uint32_t e[4];
             const bool dense = level < bfhl;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {              // k = (z bit, y bit)
-                const int yb = k & 1, zb = k >> 1;
-                const float w = (1.0f * wx) * (yb ? fy : 1.0f - fy) * (zb ? fz : 1.0f - fz);
-                const uint32_t gy = cy + (uint32_t)yb, gz = cz + (uint32_t)zb;
-                uint32_t h = dense ? (gx + gy * res + gz * res * res) : (gx ^ (gy * 2654435761u) ^ (gz * 805459861u));
-                if (mode == 1u) h &= (size - 1u);
-                else if (mode == 0u) { if (h >= size) { h -= size; if (h >= size) h %= size; } }
-                else h = h % size;
-                e[k] = L.offset[level] + h;
+                e[k] = L.offset[level] + level_index(dense, mode, size, res, cx + (uint32_t)xb, cy + (uint32_t)(k & 1), cz + (uint32_t)(k >> 1));
+                const float w = corner_weight(2 * k + xb, fr);
                 const float2 r = make_float2(f16_round(w * g.x), f16_round(w * g.y));          // cast(w * g, f16) :205-208 (f32 product first)
                 v0[k] = r.x; v1[k] = r.y;
             }

@@ -129,7 +129,7 @@ __device__ __forceinline__ void adam_mlp_pack_block(float* __restrict__ p, float
                                                     int pairs, half_t* __restrict__ wpack) {
     __shared__ float wl[9408];
     const bool skip = si[SI_SKIP] != 0;
-    const float inv_scale = sf[SF_INV_SCALE], step_size = sf[SF_LR] / sf[SF_BC1], bc2_sqrt = sf[SF_BC2_SQRT];
+    const AdamConsts ac = adam_consts(sf, beta1, beta2, eps);
     constexpr int PER = (9408 + 1023) / 1024;
     float pi[PER], gi[PER], mi[PER], vi[PER];
 #pragma unroll
@@ -142,11 +142,8 @@ __device__ __forceinline__ void adam_mlp_pack_block(float* __restrict__ p, float
         const int i = (int)threadIdx.x + 1024 * k;
         if (i >= 9408) continue;
         if (!skip) {
-            const float gr = gi[k] * inv_scale;
-            const float mk = mi[k] + (gr - mi[k]) * (1.0f - beta1);
-            const float vk = vi[k] * beta2 + gr * gr * (1.0f - beta2);
-            const float denom = sqrtf(vk) / bc2_sqrt + eps;
-            pi[k] = pi[k] - step_size * (mk / denom);
+            float mk = mi[k], vk = vi[k];
+            adam_update(pi[k], mk, vk, gi[k], ac);
             p[i] = pi[k]; m[i] = mk; v[i] = vk;
         }
         g[i] = 0.0f;
@@ -217,7 +214,9 @@ __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }
 __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 __device__ __forceinline__ float fast_rsq(float x) { return __builtin_amdgcn_rsqf(x); }
 
-// SH coefficients 4g..4g+3 of the encoded direction (x,y,z) = (d/|d| + 1)/2, spherical_harmonics.py:27-42
+// SH coefficients 4g..4g+3 of the encoded direction (x,y,z) = (d/|d| + 1)/2, spherical_harmonics.py:27-42.
+// The same sixteen expressions as sh16_quad (ngp_device.h), kept spelled out here: through sh16_quad's float4 the compiler packs the
+// products differently (v_pk_mul_f32) and the forward kernels' register count moves (profiles/shared_definitions_refactor.md).
 __device__ __forceinline__ half4 sh_quad(int g, float x, float y, float z) {
     const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
     float a, b, c, d;
@@ -243,6 +242,7 @@ __device__ __forceinline__ half4 sh_quad(int g, float x, float y, float z) {
 __device__ __forceinline__ half4 sh_quad_flat(int g, float x, float y, float z) {
     // all 16 coefficients, then a three-deep select on g: the four lane groups of a wave need different quads, and a branch per
     // quad is four exec-masked regions every wave walks through anyway -- this way the caller stays one basic block
+    // (spelled out like sh_quad above, for the same reason; the expressions are sh16_quad's)
     const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
     const float a0 = 0.28209479177387814f, b0 = -0.48860251190291987f * y, c0 = 0.48860251190291987f * z, d0 = -0.48860251190291987f * x;
     const float a1 = 1.0925484305920792f * xy, b1 = -1.0925484305920792f * yz, c1 = 0.94617469575755997f * z2 - 0.31539156525251999f,

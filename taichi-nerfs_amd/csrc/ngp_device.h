@@ -83,6 +83,25 @@ __device__ __forceinline__ float f16_round(float v) {                     // thr
     return r;
 }
 
+// SH16 coefficients 4G..4G+3 of (x, y, z) in the reference's literal form (spherical_harmonics.py:27-42 = the deployment kernels'
+// kernels.py:141-173), every product and sum a separate f32 operation in that order.  (voxel_grid.hip's sh_basis is another basis.)
+template <int G>
+__device__ __forceinline__ float4 sh16_quad(float x, float y, float z) {
+    static_assert(G >= 0 && G < 4, "SH16 has four quads");
+    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
+    if constexpr (G == 0)
+        return make_float4(0.28209479177387814f, -0.48860251190291987f * y, 0.48860251190291987f * z, -0.48860251190291987f * x);
+    else if constexpr (G == 1)
+        return make_float4(1.0925484305920792f * xy, -1.0925484305920792f * yz, 0.94617469575755997f * z2 - 0.31539156525251999f,
+                           -1.0925484305920792f * xz);
+    else if constexpr (G == 2)
+        return make_float4(0.54627421529603959f * x2 - 0.54627421529603959f * y2, 0.59004358992664352f * y * (-3.0f * x2 + y2),
+                           2.8906114426405538f * xy * z, 0.45704579946446572f * y * (1.0f - 5.0f * z2));
+    else
+        return make_float4(0.3731763325901154f * z * (5.0f * z2 - 3.0f), 0.45704579946446572f * x * (1.0f - 5.0f * z2),
+                           1.4453057213202769f * z * (x2 - y2), 0.59004358992664352f * x * (-x2 + 3.0f * y2));
+}
+
 // modules/utils.py:54-57
 __device__ __forceinline__ float calc_dt(float t, float esf, float dt_min, float dt_max) {
     return fminf(dt_max, fmaxf(dt_min, t * esf));
@@ -249,7 +268,24 @@ __device__ __forceinline__ uint32_t f32_to_bf16_bits(float f) {
 // round-to-nearest-even f32 -> f16 bits (the per-forward cast of hash_encoder_half.py:367)
 __device__ __forceinline__ uint32_t f32_to_f16_bits(float f) { return (uint32_t)__half_as_ushort(__float2half_rn(f)); }
 
-// torch.optim.Adam(eps) arithmetic on float4s, grid-stride over `n_blocks` blocks of which this is `block`; unscales the
+// torch.optim.Adam(eps)'s update of ONE parameter, the only spelling of it in the library: the dense table pass below, the optimizer
+// in the scatter-add's flush (hash_bwd_lds.hip) and the MLP weights (mlp.hip) must give bit-identical parameters and moments
+// (tests/test_gpu_flush_adam.py).  The constants are read from the optimizer state once per kernel.
+struct AdamConsts {
+    float inv_scale, step_size /* lr / bc1 */, bc2_sqrt, beta1, beta2, eps;
+};
+__device__ __forceinline__ AdamConsts adam_consts(const float* __restrict__ sf, float beta1, float beta2, float eps) {
+    return {sf[SF_INV_SCALE], sf[SF_LR] / sf[SF_BC1], sf[SF_BC2_SQRT], beta1, beta2, eps};
+}
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float g, const AdamConsts& c) {
+    const float gr = g * c.inv_scale;                                        // GradScaler.unscale_, on the fly
+    m = m + (gr - m) * (1.0f - c.beta1);
+    v = v * c.beta2 + gr * gr * (1.0f - c.beta2);
+    const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+    p = p - c.step_size * (m / denom);
+}
+
+// adam_update on float4s, grid-stride over `n_blocks` blocks of which this is `block`; unscales the
 // gradient on the fly and zero-fills it.
 // SHADOW: also refresh a 16-bit storage copy of the parameters (1 = bf16, 2 = f16).  GRAD16: the gradient buffer is f16 (the
 // half2 encoder's, hash_encoder_half.py:350-358) and is widened to f32 here, like autograd does for the fp32 master parameter.
@@ -259,7 +295,7 @@ __device__ __forceinline__ void adam_table_pass(float4* __restrict__ p, void* __
                                                 const int32_t* __restrict__ si, float beta1, float beta2, float eps,
                                                 uint2* __restrict__ shadow, long block, long n_blocks) {
     const bool skip = si[SI_SKIP] != 0;
-    const float inv_scale = sf[SF_INV_SCALE], step_size = sf[SF_LR] / sf[SF_BC1], bc2_sqrt = sf[SF_BC2_SQRT];
+    const AdamConsts ac = adam_consts(sf, beta1, beta2, eps);
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     float4* g32 = reinterpret_cast<float4*>(gv);
     uint2* g16 = reinterpret_cast<uint2*>(gv);
@@ -286,16 +322,8 @@ __device__ __forceinline__ void adam_table_pass(float4* __restrict__ p, void* __
         if (!g_any && mi.x == 0.f && mi.y == 0.f && mi.z == 0.f && mi.w == 0.f && vi.x == 0.f && vi.y == 0.f && vi.z == 0.f && vi.w == 0.f)
             continue;
         float4 pi = p[i];
-#define NGP_ADAM1(c)                                                          \
-        {                                                                     \
-            const float gr = gi.c * inv_scale;                                \
-            mi.c = mi.c + (gr - mi.c) * (1.0f - beta1);                       \
-            vi.c = vi.c * beta2 + gr * gr * (1.0f - beta2);                   \
-            const float denom = sqrtf(vi.c) / bc2_sqrt + eps;                 \
-            pi.c = pi.c - step_size * (mi.c / denom);                         \
-        }
-        NGP_ADAM1(x) NGP_ADAM1(y) NGP_ADAM1(z) NGP_ADAM1(w)
-#undef NGP_ADAM1
+        adam_update(pi.x, mi.x, vi.x, gi.x, ac); adam_update(pi.y, mi.y, vi.y, gi.y, ac);
+        adam_update(pi.z, mi.z, vi.z, gi.z, ac); adam_update(pi.w, mi.w, vi.w, gi.w, ac);
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (g_any) { if constexpr (GRAD16) g16[i] = make_uint2(0u, 0u); else g32[i] = zero; }
         if constexpr (SHADOW == 1)

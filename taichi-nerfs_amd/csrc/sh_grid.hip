@@ -10,26 +10,8 @@ namespace ngp {
 __global__ void __launch_bounds__(256) sh16_fwd_kernel(const float* __restrict__ dirs, int n, float4* __restrict__ out) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float x = dirs[3 * (size_t)i], y = dirs[3 * (size_t)i + 1], z = dirs[3 * (size_t)i + 2];
-        const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-        float4 a, b, c, d;
-        a.x = 0.28209479177387814f;                                   // spherical_harmonics.py:27-42, literal forms
-        a.y = -0.48860251190291987f * y;
-        a.z = 0.48860251190291987f * z;
-        a.w = -0.48860251190291987f * x;
-        b.x = 1.0925484305920792f * xy;
-        b.y = -1.0925484305920792f * yz;
-        b.z = 0.94617469575755997f * z2 - 0.31539156525251999f;
-        b.w = -1.0925484305920792f * xz;
-        c.x = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-        c.y = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-        c.z = 2.8906114426405538f * xy * z;
-        c.w = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-        d.x = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-        d.y = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-        d.z = 1.4453057213202769f * z * (x2 - y2);
-        d.w = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
         float4* o = out + 4 * (size_t)i;
-        o[0] = a; o[1] = b; o[2] = c; o[3] = d;
+        o[0] = sh16_quad<0>(x, y, z); o[1] = sh16_quad<1>(x, y, z); o[2] = sh16_quad<2>(x, y, z); o[3] = sh16_quad<3>(x, y, z);
     }
 }
 

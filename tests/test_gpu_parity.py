@@ -355,6 +355,75 @@ def test_hash_bwd_f32_sliced(oracle, hip_lib, max_res):
     np.testing.assert_allclose(got, dt3.cpu().numpy(), rtol=2e-5, atol=2e-5)
 
 
+@pytest.fixture(scope="module")
+def real_modulo_bwd_inputs():
+    """~5,800 samples for test_hash_bwd_real_modulo_levels: ray-like runs (equal-cell pre-summing, the hit queue), uniform points, the
+    box's corners, every seventh gradient row zero -- more than one 4096-sample super-chunk, not a multiple of 64."""
+    rng = np.random.default_rng(12)
+    n_rays, per_ray = 96, 50
+    o = rng.random((n_rays, 1, 3), dtype=np.float32) * 0.8 + 0.1
+    d = rng.standard_normal((n_rays, 1, 3)).astype(np.float32)
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    t = (np.arange(per_ray, dtype=np.float32) * np.float32(0.0017))[None, :, None]
+    x = np.clip(o + d * t, 0.0, 1.0).reshape(-1, 3).astype(np.float32)
+    x = np.concatenate([x, rng.random((1003, 3), dtype=np.float32),
+                        np.array([[0, 0, 0], [1, 1, 1], [1, 0, 1], [0.999999, 1e-7, 0.5]], np.float32)])
+    dout = rng.standard_normal((x.shape[0], 32)).astype(np.float32)
+    dout[::7] = 0.0
+    assert x.shape[0] > 4096 and x.shape[0] % 64 != 0
+    return x, dout
+
+
+@pytest.mark.parametrize("max_params", [3 * 2**17, 2**19 - 8, 100000])
+def test_hash_bwd_real_modulo_levels(oracle, hip_lib, monkeypatch, real_modulo_bwd_inputs, max_params):
+    """The scatter-add forms on the tables of test_hash_fwd_f32_real_modulo_levels, whose hashed levels index with the real
+    `hash % size` (level_index mode 2, csrc/hash_common.h): the LDS-sliced kernel (its generic accumulate and the prepass's generic
+    bitmap form -- the two-multiply hashed forms must NOT be taken there), the float-atomic kernel, and for one table the half2
+    encoder's sliced form.  Same touched entries and values as the oracle, at the bars of test_hash_bwd_f32_sliced /
+    test_hash_bwd_f16_sliced."""
+    lv = ops.make_levels(max_params, 16, 16, 1024, 2)
+    sizes = [int(v) for v in np.ctypeslib.as_array(lv.map_size)[:16]]
+    assert any(v & (v - 1) for v in sizes[int(lv.begin_fast_hash_level):])       # at least one hashed level needs the real modulo
+    x, dout = real_modulo_bwd_inputs
+    n = x.shape[0]
+    ref = oracle.hash_bwd_f32(x, dout, lv)
+    dt = torch.zeros(lv.total_entries * 2, device="cuda")
+    ops.hash_bwd_f32_sliced(dev(x), dev(dout), lv, dt)
+    got = dt.cpu().numpy()
+    assert support_matches(ref, got)
+    np.testing.assert_allclose(got, ref, rtol=2e-5, atol=2e-5)
+    # the float-atomic kernel, through the operator
+    L = ops._lib()
+    calls = []
+    real = L.ngp_hash_bwd_f32_sliced
+    monkeypatch.setattr(L, "ngp_hash_bwd_f32_sliced", lambda *a: (calls.append(1), real(*a))[1])
+    monkeypatch.setenv("NGP_HASH_BWD", "atomic")
+    got = ops.hash_bwd_f32(dev(x), dev(dout), lv, torch.zeros(lv.total_entries * 2, device="cuda")).cpu().numpy()
+    assert calls == []
+    assert support_matches(ref, got)
+    np.testing.assert_allclose(got, ref, rtol=2e-5, atol=2e-5)
+    if max_params != 3 * 2**17:
+        return
+    # the half2 encoder's sliced form, on the table whose hashed levels all take the real modulo AND have one owner per slice (the
+    # 100000-entry levels are replicated over sample ranges).  Tolerances as in test_hash_bwd_f16_sliced (gradients of the same 1e-2
+    # scale): one fp16 rounding of the exact sum on the single-owner levels, the packed-f16-atomic bar on the replicated dense ones;
+    # the plan says which is which.
+    nrep = (ctypes.c_uint8 * 16)()
+    mm = ctypes.c_uint32()
+    assert L.ngp_hash_bwd_sliced_plan(ctypes.byref(lv), None, 0, None, None, nrep, ctypes.byref(mm), None) > 0
+    first = min(l for l in range(16) if all(nrep[k] == 1 for k in range(l, 16)))
+    assert first == int(lv.begin_fast_hash_level)                                 # the tight bar covers every hashed level
+    split = int(lv.offset[first])
+    dout_h = (dout * np.float32(1e-2)).astype(np.float32)
+    ref_h = oracle.hash_bwd_f16(x, dout_h.reshape(n, 16, 2).astype(np.float16), lv)
+    g = torch.zeros(lv.total_entries, 2, device="cuda", dtype=torch.float16)
+    ops.hash_bwd_f16_sliced(dev(x), dev(dout_h), lv, g)
+    got_h = g.float().cpu().numpy()
+    assert support_matches(ref_h, got_h)
+    np.testing.assert_allclose(got_h[split:], ref_h[split:], rtol=1.5e-3, atol=8e-6)
+    np.testing.assert_allclose(got_h[:split], ref_h[:split], rtol=3e-2, atol=2e-3)
+
+
 def test_hash_bwd_f32_sliced_concentrated_plan(oracle, hip_lib):
     """Round 5: the concentrated plan (NGP_BWD_PLAN_CONCENTRATED in the level table) -- coarse hashed levels with sample-range replicas -- on the C3
     table with points crowded into 2 % of the box (what a multi-cascade scene looks like to the coarse levels): same touched entries
