@@ -219,6 +219,26 @@ int ngp_voxel_density(const float* xyzs, const float* density, int n, int grid_s
 int ngp_voxel_bwd(const float* xyzs, const float* dirs, const float* sigmas, const float* rgbs, const float* dsigmas /*[n]*/,
                   const float* drgbs /*[n,3]*/, int n, int grid_size, int sh_degree, float grid_min, float grid_radius, float* dsh,
                   float* ddensity, void* stream);
+/* Trilinear form of the three calls above: query_grids(use_trilinear=True) (:546-561) with trilinear_interpolation (:524-533) and
+ * out_of_grid (:489-508); upstream's arithmetic behind that switch cannot run, so the contract is stated here (voxel grid).
+ * u = (p - grid_min) / grid_radius per axis (f32, IEEE divide), b = floor(u), f = u - b; the corners are b + (i, j, k), i, j, k in
+ * {0, 1}.  A corner with a coordinate outside [0, G) reads the all-zero row and gets no gradient, without renormalisation (grid_sample's
+ * zero padding with align_corners); a sample with any u < -1, u >= G or NaN gives sigma = 0, rgb = 0.5 and no gradient.  The raw row
+ * (3*D SH coefficients and the density) is interpolated by nested lerps a + t (b - a), z first, then y, then x -- this form returns a
+ * constant field exactly -- and then activated: sigma = relu(density), rgb_c = sigmoid(sum_k Y_k sh_{c,k}) (the three dot products
+ * are formed per corner and interpolated: eval_sh is linear). */
+int ngp_voxel_trilinear_fwd(const float* xyzs /*[n,3]*/, const float* dirs /*[n,3], any length*/, const float* sh, const float* density,
+                            int n, int grid_size, int sh_degree, float grid_min, float grid_radius, float* sigmas /*[n]*/,
+                            float* rgbs /*[n,3]*/, void* stream);
+/* Density only, bit for bit the sigmas of ngp_voxel_trilinear_fwd (the occupancy update's query, networks.py:255-290). */
+int ngp_voxel_trilinear_density(const float* xyzs, const float* density, int n, int grid_size, float grid_min, float grid_radius,
+                                float* sigmas, void* stream);
+/* Backward of ngp_voxel_trilinear_fwd from the saved sigmas / rgbs: with w the product of the corner's per-axis factors (1 - f or f),
+ * ddensity[corner] += w [sigma > 0] dsigma and dsh[corner, c, k] += w drgb_c rgb_c (1 - rgb_c) Y_k; the fields are not read.  dsh /
+ * ddensity must be zero-filled by the caller (or hold a gradient to accumulate into); float atomics: the order is not fixed. */
+int ngp_voxel_trilinear_bwd(const float* xyzs, const float* dirs, const float* sigmas, const float* rgbs, const float* dsigmas /*[n]*/,
+                            const float* drgbs /*[n,3]*/, int n, int grid_size, int sh_degree, float grid_min, float grid_radius,
+                            float* dsh, float* ddensity, void* stream);
 /* packbits (utils.py:157-169) of VoxelGrid.update_density_grid: bit = density >= threshold and density > 0, threshold =
  * min(mean of the positive cells, density_threshold), the mean summed in f64 in a fixed order.  NGP's packbits (`>` against an f32
  * mean) marks none or all cells of a fresh grid that holds one value everywhere, depending on how the mean rounds.

@@ -4,7 +4,8 @@ step with procedural Lego rays.  The occupancy grid is the trained-Lego 128^3 bi
 refined to 256^3 (every cell's eight children inherit its bit).  Prints ONE JSON line: rays/s, and the per-step split between the
 forward (march + voxel_fwd + composite), the backward (composite bwd + gradient zero-fill + voxel_bwd), the zero-fill alone and the
 optimizer step (dense Adam over both fields), from CUDA events.
-    python profiles/microbench/voxel_dropin.py [--steps 30] [--warmup 5] [--rays 8192]"""
+`--trilinear` runs the model with use_trilinear=True (the eight-corner lookup) instead of the nearest voxel.
+    python profiles/microbench/voxel_dropin.py [--steps 30] [--warmup 5] [--rays 8192] [--trilinear]"""
 import argparse
 import json
 import os
@@ -30,11 +31,34 @@ def refined_lego_bitfield(dev, G=256):
     return (occ * weights).sum(1).to(torch.uint8)
 
 
+def atomic_bytes_per_sample(xyzs, model):
+    """Replay of the backward's merge rule on one step's samples (every sample taken as contributing): a wave of 64 consecutive samples
+    issues one add per channel of every run of equal rows (nearest) or, trilinear, of every valid corner of every run of equal base
+    cells.  Returns (bytes per sample, samples per run)."""
+    G, W = model.grid_size, 3 * model.sh_dim + 1
+    u = (xyzs.float() - np.float32(model.grid_min)) / np.float32(model.grid_radius)
+    if model.use_trilinear:
+        ok = ((u >= -1) & (u < G)).all(1)
+        b = torch.floor(u).long()
+        key = ((b[:, 0] + 1) * (G + 1) + b[:, 1] + 1) * (G + 1) + b[:, 2] + 1
+        corners = ((b >= 0).long() + (b + 1 < G).long()).prod(1)
+    else:
+        b = torch.round(u).long()
+        ok = ((b >= 0) & (b < G)).all(1)
+        key = (b[:, 0] * G + b[:, 1]) * G + b[:, 2]
+        corners = torch.ones_like(key)
+    key = torch.where(ok, key, torch.full_like(key, -1))
+    lane = torch.arange(key.numel(), device=key.device) % 64
+    head = ((lane == 0) | (key != torch.roll(key, 1))) & (key >= 0)
+    return float(corners[head].sum()) * W * 4 / key.numel(), float(ok.sum()) / max(int(head.sum()), 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rays", type=int, default=8192)
+    ap.add_argument("--trilinear", action="store_true")
     args = ap.parse_args()
     import apex
     from modules.networks import MODEL_DICT
@@ -44,7 +68,7 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     model = MODEL_DICT["svox"](scale=0.5, half_opt=False, sh_degree=2, grid_size=256, grid_radius=0.0125, origin_sh=0.,
-                               origin_sigma=0.1).to(dev)
+                               origin_sigma=0.1, use_trilinear=args.trilinear).to(dev)
     with torch.no_grad():
         model.sh_fields.uniform_(-0.5, 0.5)
         model.density_fields.uniform_(0.0, 30.0)
@@ -97,13 +121,20 @@ def main():
         torch.zeros_like(model.sh_fields); torch.zeros_like(model.density_fields)
     z1.record()
     torch.cuda.synchronize()
+    # one step's samples for the atomic-byte replay
+    from ngp_hip import ops
+    o, d, _ = batches[0]
+    hits = ops.ray_aabb(o, d, 0.5)
+    _, xyzs, *_ = ops.march_train(o, d, hits, model.density_bitfield, torch.rand(args.rays, device=dev), 1, 0.5, 0.0, 256, 1024)
+    bps, per_run = atomic_bytes_per_sample(xyzs, model)
     n = args.steps
     sh_bytes = model.sh_fields.numel() * 4
     print(json.dumps({"metric": "voxel_dropin_rays_per_sec", "rays_per_sec": args.rays * n / dt, "rays": args.rays, "steps": n,
-                      "warmup": args.warmup, "ms_per_step": 1e3 * dt / n, "grid_size": 256, "sh_degree": 2,
+                      "warmup": args.warmup, "ms_per_step": 1e3 * dt / n, "grid_size": 256, "sh_degree": 2, "trilinear": args.trilinear,
                       "samples_per_step": float(np.mean([int(s) for s in samples])),
                       "split_ms_per_step": {"forward": split["forward"] / n, "backward": split["backward"] / n,
                                             "zero_fill_of_backward": z0.elapsed_time(z1) / n, "adam": split["adam"] / n},
+                      "bwd_atomic_bytes_per_sample": bps, "samples_per_run": per_run, "replay_samples": int(xyzs.shape[0]),
                       "field_bytes": sh_bytes + model.density_fields.numel() * 4,
                       "device": torch.cuda.get_device_name(0)}))
 

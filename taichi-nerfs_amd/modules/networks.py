@@ -11,6 +11,7 @@ from torch import nn
 
 import os
 
+from ngp_hip import experiment as _exp
 from ngp_hip import ops as _ops
 from .rendering import NEAR_DISTANCE
 from .spherical_harmonics import DirEncoder
@@ -311,14 +312,15 @@ class MLP(nn.Module):
 
 
 class _VoxelShade(torch.autograd.Function):
-    """ngp_voxel_fwd / ngp_voxel_bwd: nearest-voxel lookup, relu density, sigmoid(eval_sh) colour; the backward adds into freshly
-    zeroed dense gradients of both fields."""
+    """ngp_voxel_fwd / ngp_voxel_bwd (trilinear: ngp_voxel_trilinear_fwd / _bwd): nearest-voxel or trilinear lookup, relu density,
+    sigmoid(eval_sh) colour; the backward adds into freshly zeroed dense gradients of both fields."""
 
     @staticmethod
-    def forward(ctx, x, d, sh_fields, density_fields, cfg):
-        sigmas, rgbs = _ops.voxel_fwd(x, d, sh_fields, density_fields, *cfg)
+    def forward(ctx, x, d, sh_fields, density_fields, cfg, trilinear):
+        sigmas, rgbs = _ops.voxel_fwd(x, d, sh_fields, density_fields, *cfg, trilinear=trilinear)
         ctx.save_for_backward(x, d, sigmas, rgbs)
         ctx.cfg = cfg
+        ctx.trilinear = trilinear
         ctx.shapes = (sh_fields.shape, density_fields.shape)
         ctx.set_materialize_grads(False)
         return sigmas, rgbs
@@ -331,8 +333,8 @@ class _VoxelShade(torch.autograd.Function):
         g_rgbs = torch.zeros_like(rgbs) if g_rgbs is None else g_rgbs.contiguous().float()
         dsh = torch.zeros(ctx.shapes[0], device=x.device, dtype=torch.float32)
         ddensity = torch.zeros(ctx.shapes[1], device=x.device, dtype=torch.float32)
-        _ops.voxel_bwd(x, d, sigmas, rgbs, g_sigmas, g_rgbs, G, deg, m, r, dsh, ddensity)
-        return None, None, dsh, ddensity, None
+        _ops.voxel_bwd(x, d, sigmas, rgbs, g_sigmas, g_rgbs, G, deg, m, r, dsh, ddensity, trilinear=ctx.trilinear)
+        return None, None, dsh, ddensity, None, None
 
 
 class VoxelGrid(nn.Module):
@@ -344,11 +346,19 @@ class VoxelGrid(nn.Module):
     the occupancy buffers.  The lookup is the one the reference's helpers describe (normalize_samples, query_grids with
     use_trilinear=False, out_of_grid) with PlenOctrees' activations: sigma = relu(density), rgb = sigmoid(eval_sh(deg, sh_c, d/|d|))
     per channel (channel-major coefficients).  Both directions are the HIP kernels ngp_voxel_fwd / ngp_voxel_bwd (voxel
-    grid).  `half_opt` is accepted and ignored (upstream: "available for hash")."""
+    grid).  `half_opt` is accepted and ignored (upstream: "available for hash").
+
+    `use_trilinear` (query_grids' switch, :546-561): True interpolates the eight grid points around the sample (zero outside the grid,
+    ngp_voxel_trilinear_fwd / _density / _bwd) in forward, density and the backward; False reads the nearest one.  None, the default,
+    is False unless NGP_EXPERIMENT carries svox_trilinear=1 -- the reference's train.py, whose opt.py has no flag for it, reaches the
+    lookup that way.  The state_dict is the same in both modes."""
 
     def __init__(self, scale: float = 0.5, half_opt: bool = False, sh_degree: int = 2, grid_size: int = 256,
-                 grid_radius: float = 0.0125, origin_sh: float = 0., origin_sigma: float = 0.1):
+                 grid_radius: float = 0.0125, origin_sh: float = 0., origin_sigma: float = 0.1, use_trilinear=None):
         super().__init__()
+        if use_trilinear is None:
+            use_trilinear = _exp.get("svox_trilinear", "0") == "1"
+        self.use_trilinear = bool(use_trilinear)
         if not isinstance(sh_degree, (int, np.integer)) or not 0 <= sh_degree <= 4:
             raise ValueError("sh_degree must be 0-4 (sh_utils.eval_sh), got %r" % (sh_degree,))
         G = grid_size
@@ -394,14 +404,16 @@ class VoxelGrid(nn.Module):
     # ------------------------------------------------------------------------------------------ shading
     def forward(self, x, d):
         """x: [N,3] positions, d: [N,3] directions (any length) -> (sigmas [N], rgbs [N,3]), fp32 with or without autocast."""
-        return _VoxelShade.apply(x.contiguous().float(), d.contiguous().float(), self.sh_fields, self.density_fields, self._cfg())
+        return _VoxelShade.apply(x.contiguous().float(), d.contiguous().float(), self.sh_fields, self.density_fields, self._cfg(),
+                                 self.use_trilinear)
 
     def density(self, x):
         """x: [N,3] -> sigmas [N] (differentiable w.r.t. density_fields when grad mode is on)."""
         x = x.contiguous().float()
         if torch.is_grad_enabled() and self.density_fields.requires_grad:
             return self.forward(x, torch.ones_like(x))[0]
-        return _ops.voxel_density(x, self.density_fields, self.grid_size, self.grid_min, float(self.grid_radius))
+        return _ops.voxel_density(x, self.density_fields, self.grid_size, self.grid_min, float(self.grid_radius),
+                                  trilinear=self.use_trilinear)
 
     # ------------------------------------------------------------------------------------------ occupancy grid
     get_all_cells = NGP.get_all_cells

@@ -23,6 +23,8 @@ KEYS = {
     "bwd_concentrated": "1 / 0: the scatter-add's concentrated-scene task plan (unset: on for multi-cascade scenes)",
     "mlp_dw": "atomic: round 3's float-atomic weight gradients instead of per-block slabs",
     "mlp_dw_reduce": "prologue: the slab sum in the prologue launch instead of the head of the scatter-add launch",
+    # ---- the voxel-grid model (model_name='svox')
+    "svox_trilinear": "1: VoxelGrid(use_trilinear=None) interpolates the eight surrounding grid points instead of reading the nearest (how the reference's train.py, which has no flag for it, reaches the lookup)",
     # ---- the overlapped multi-GPU exchange (default off until a multi-GPU run has decided)
     "comm_overlap": "1: one scatter-add launch + async reduce-scatter / Adam / all-gather per level group",
     "comm_groups": "first level of each group in launch order (default '8,0')",

@@ -197,6 +197,9 @@ SIGNATURES = {
     "ngp_voxel_fwd": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
     "ngp_voxel_density": [_P, _P, _I, _I, _F, _F, _P, _P],
     "ngp_voxel_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
+    "ngp_voxel_trilinear_fwd": [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
+    "ngp_voxel_trilinear_density": [_P, _P, _I, _I, _F, _F, _P, _P],
+    "ngp_voxel_trilinear_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _P, _P, _P],
     "ngp_voxel_occ_scratch_doubles": [],
     "ngp_voxel_occ_pack": [_P, ctypes.c_longlong, ctypes.c_double, _P, _P, _P],
     "ngp_deploy_shade": [_P, _P, _P, _LV, _P, _P, _I, _P, _P, _P, _P],

@@ -370,9 +370,10 @@ def _voxel_fields(sh, density, grid_size, sh_degree):
         raise ValueError("voxel fields must be [G,G,G,3*D] and [G,G,G,1] for G=%d, degree %d" % (G, sh_degree))
 
 
-def voxel_fwd(xyzs, dirs, sh, density, grid_size, sh_degree, grid_min, grid_radius):
-    """positions [n,3], directions [n,3] -> (sigmas [n], rgbs [n,3]): nearest voxel of (p - grid_min) / grid_radius, relu density,
-    sigmoid of eval_sh per channel (VoxelGrid, modules/networks.py)."""
+def voxel_fwd(xyzs, dirs, sh, density, grid_size, sh_degree, grid_min, grid_radius, trilinear=False):
+    """positions [n,3], directions [n,3] -> (sigmas [n], rgbs [n,3]): nearest voxel of (p - grid_min) / grid_radius (trilinear: the
+    eight surrounding grid points interpolated, zero outside the grid), relu density, sigmoid of eval_sh per channel (VoxelGrid,
+    modules/networks.py)."""
     _dev(xyzs, torch.float32, "xyzs"); _dev(dirs, torch.float32, "dirs")
     _voxel_fields(sh, density, grid_size, sh_degree)
     n = xyzs.shape[0]
@@ -380,12 +381,13 @@ def voxel_fwd(xyzs, dirs, sh, density, grid_size, sh_degree, grid_min, grid_radi
         raise ValueError("voxel_fwd: xyzs and dirs must both be [n, 3], got %s and %s" % (tuple(xyzs.shape), tuple(dirs.shape)))
     sigmas = torch.empty(n, device=xyzs.device, dtype=torch.float32)
     rgbs = torch.empty(n, 3, device=xyzs.device, dtype=torch.float32)
-    check(_lib().ngp_voxel_fwd(_ptr(xyzs), _ptr(dirs), _ptr(sh), _ptr(density), n, int(grid_size), int(sh_degree), float(grid_min),
-                               float(grid_radius), _ptr(sigmas), _ptr(rgbs), _stream()), "ngp_voxel_fwd")
+    name = "ngp_voxel_trilinear_fwd" if trilinear else "ngp_voxel_fwd"
+    check(getattr(_lib(), name)(_ptr(xyzs), _ptr(dirs), _ptr(sh), _ptr(density), n, int(grid_size), int(sh_degree), float(grid_min),
+                                float(grid_radius), _ptr(sigmas), _ptr(rgbs), _stream()), name)
     return sigmas, rgbs
 
 
-def voxel_density(xyzs, density, grid_size, grid_min, grid_radius, out=None):
+def voxel_density(xyzs, density, grid_size, grid_min, grid_radius, out=None, trilinear=False):
     _dev(xyzs, torch.float32, "xyzs"); _dev(density, torch.float32, "density_fields")
     if density.numel() != int(grid_size)**3:
         raise ValueError("density_fields must hold G^3 values")
@@ -393,21 +395,24 @@ def voxel_density(xyzs, density, grid_size, grid_min, grid_radius, out=None):
     if xyzs.shape != (n, 3) or (out is not None and (out.shape != (n,) or not out.is_contiguous() or out.dtype != torch.float32)):
         raise ValueError("voxel_density: xyzs must be [n, 3] and out a contiguous f32 [n]")
     sigmas = torch.empty(n, device=xyzs.device, dtype=torch.float32) if out is None else out
-    check(_lib().ngp_voxel_density(_ptr(xyzs), _ptr(density), n, int(grid_size), float(grid_min), float(grid_radius), _ptr(sigmas),
-                                   _stream()), "ngp_voxel_density")
+    name = "ngp_voxel_trilinear_density" if trilinear else "ngp_voxel_density"
+    check(getattr(_lib(), name)(_ptr(xyzs), _ptr(density), n, int(grid_size), float(grid_min), float(grid_radius), _ptr(sigmas),
+                                _stream()), name)
     return sigmas
 
 
-def voxel_bwd(xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, grid_size, sh_degree, grid_min, grid_radius, dsh, ddensity):
-    """dsh += d loss / d sh_fields, ddensity += d loss / d density_fields (both zero-filled by the caller)."""
+def voxel_bwd(xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, grid_size, sh_degree, grid_min, grid_radius, dsh, ddensity, trilinear=False):
+    """dsh += d loss / d sh_fields, ddensity += d loss / d density_fields (both zero-filled by the caller); trilinear: of the forward
+    with trilinear=True."""
     for t, name in ((xyzs, "xyzs"), (dirs, "dirs"), (sigmas, "sigmas"), (rgbs, "rgbs"), (dsigmas, "dsigmas"), (drgbs, "drgbs")):
         _dev(t, torch.float32, name)
     _voxel_fields(dsh, ddensity, grid_size, sh_degree)
     n = xyzs.shape[0]
     if dirs.shape != (n, 3) or sigmas.shape != (n,) or rgbs.shape != (n, 3) or dsigmas.shape != (n,) or drgbs.shape != (n, 3):
         raise ValueError("voxel_bwd: per-sample tensors must be [n], [n,3]")
-    check(_lib().ngp_voxel_bwd(_ptr(xyzs), _ptr(dirs), _ptr(sigmas), _ptr(rgbs), _ptr(dsigmas), _ptr(drgbs), n, int(grid_size),
-                               int(sh_degree), float(grid_min), float(grid_radius), _ptr(dsh), _ptr(ddensity), _stream()), "ngp_voxel_bwd")
+    name = "ngp_voxel_trilinear_bwd" if trilinear else "ngp_voxel_bwd"
+    check(getattr(_lib(), name)(_ptr(xyzs), _ptr(dirs), _ptr(sigmas), _ptr(rgbs), _ptr(dsigmas), _ptr(drgbs), n, int(grid_size),
+                                int(sh_degree), float(grid_min), float(grid_radius), _ptr(dsh), _ptr(ddensity), _stream()), name)
     _touched(dsh, ddensity)
     return dsh, ddensity
 
