@@ -28,8 +28,11 @@
 // activate and re-pack): everything between two MFMAs uses the packed f16 instructions (profiles/microbench/
 // r01_mlp_bwd_breakdown.txt).
 //
-// Numerics are tolerance-checked against an fp32 torch restatement and against torch's own autocast path
-// (tests/test_gpu_mlp.py); bf16/fp16 MFMA is used because this is the one genuine dense contraction on the path.
+// Numerics: the rounding points above are a contract, restated in float64 by tests/mlp_reference.py.  tests/test_gpu_mlp_exact.py
+// holds both kernels to it element by element -- sigma to expf's accuracy, rgb to one fp16 ulp, d_enc and dW to twice the model's
+// running error bound -- in every entry point and layout, at one trip / round of the persistent loops and at more than one;
+// tests/test_gpu_mlp.py adds the norm-wise comparison with an fp32 torch restatement and with torch's own autocast path.
+// bf16/fp16 MFMA is used because this is the one genuine dense contraction on the path.
 #include "ngp_device.h"
 #include <stdlib.h>
 
@@ -297,6 +300,11 @@ __device__ __forceinline__ void tile_forward_frags(const WF& W, int g, const flo
     const float inv = fast_rsq(dx * dx + dy * dy + dz * dz);
     const float x = (dx * inv + 1.0f) / 2.0f, y = (dy * inv + 1.0f) / 2.0f, z = (dz * inv + 1.0f) / 2.0f;
     t.b_in3 = cat_h4(FLAT_SH ? sh_quad_flat(g, x, y, z) : sh_quad(g, x, y, z), t.h);
+    // A direction of length 0 (or with a non-finite component) makes x, y, z NaN, and nn.ReLU hands a NaN on to rgb.  relu_h4 does
+    // not: v_pk_max_f16 returns the number where one operand is NaN, so layer 3 would come out as zeros and rgb as sigmoid(0).
+    // 0 * (x + y + z) is NaN exactly then and +-0 otherwise; added to the three colour pre-activations it carries the NaN past the
+    // two ReLUs and changes no bit of any other sample (tests/test_gpu_mlp_exact.py, test_zero_length_direction).
+    const float nan_dir = 0.0f * (x + y + z);
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) t.a3[mt] = relu_h4(NGP_MFMA(W(F_W3 + mt), t.b_in3, zero));
     const half8 b30 = cat_h4(t.a3[0], t.a3[1]), b31 = cat_h4(t.a3[2], t.a3[3]);
@@ -310,7 +318,7 @@ __device__ __forceinline__ void tile_forward_frags(const WF& W, int g, const flo
     d5 = NGP_MFMA(W(F_W5 + 1), cat_h4(t.a4[2], t.a4[3]), d5);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const float c = (float)(half_t)d5[r];
+        const float c = (float)(half_t)d5[r] + nan_dir;
         t.rgb[r] = (half_t)fast_rcp(1.0f + fast_exp(-c));
     }
 }

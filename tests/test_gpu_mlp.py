@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from mlp_reference import to_pairs as _to_pairs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -121,16 +123,6 @@ def test_ngp_forward_uses_fused_path_under_autocast(hip_lib):
     torch.testing.assert_close(dens, s1, rtol=0, atol=0)
 
 
-def _to_pairs(enc_nat, n_max):
-    """[n,32] natural (level-major) -> pair-major planes [8, n_max, 4] (include/ngp_hip.h, enc_pairs)."""
-    n = enc_nat.shape[0]
-    out = torch.zeros(8, n_max, 4, device=enc_nat.device, dtype=enc_nat.dtype)
-    for p in range(8):
-        out[p, :n, 0:2] = enc_nat[:, 2 * p:2 * p + 2]
-        out[p, :n, 2:4] = enc_nat[:, 2 * (15 - p):2 * (15 - p) + 2]
-    return out
-
-
 def test_pair_major_layout_equals_natural_layout(hip_lib):
     """The fused path's pair-major encoding planes are a pure re-indexing: hash fwd bit-exact, MLP fwd/bwd equal up to the
     fp32 summation order inside one K=32 MFMA step, hash bwd equal up to atomic order."""
@@ -180,7 +172,9 @@ def test_pair_major_layout_equals_natural_layout(hip_lib):
 def test_backward_forms_and_slab_reduction(hip_lib, monkeypatch, form, n):
     """The backward kernel (the LDS-image form; a -DNGP_MLP_BWD_REG build also answers NGP_EXPERIMENT mlp_bwd=reg) and both
     ways the weight gradients leave it -- float atomics on dW, or per-block slabs + ngp_mlp_dw_reduce (what the trainer
-    uses) -- give the same d_enc bit for bit and the same dW up to the summation order; a live list in reverse order too."""
+    uses) -- give the same d_enc bit for bit and the same dW up to the summation order; a live list in reverse order too.
+    This compares the kernel with itself: the truth for both ways out, at one round and at more than one, is the float64 model of
+    tests/test_gpu_mlp_exact.py (test_backward_per_element)."""
     import ctypes
     from ngp_hip import lib, ops
     from ngp_hip.ops import _ptr, _stream
