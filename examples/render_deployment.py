@@ -96,7 +96,8 @@ def main():
     ap.add_argument("--res_h", type=int, default=600)
     ap.add_argument("--pose_index", type=int, default=20)
     ap.add_argument("--out", default="deployment_render")
-    ap.add_argument("--mode", default="oneshot", choices=["oneshot", "progressive"])
+    ap.add_argument("--mode", default="oneshot", choices=["oneshot", "progressive", "fused"],
+                    help="oneshot: march / shade / composite operators; progressive: the reference's rounds; fused: one launch per frame")
     ap.add_argument("--train_steps", type=int, default=0, help="train the deployment configuration on the procedural scene first")
     ap.add_argument("--workdir", default="results/deployment", help="where --train_steps writes deployment.npy and the blobs")
     ap.add_argument("--bin_dtype", default="float32", choices=["float32", "float16"])

@@ -614,6 +614,22 @@ int ngp_occ_pack(const float* density_grid, float* stats, float density_threshol
 int ngp_deploy_shade(const float* xyzs, const float* dirs, const float* table, const ngp_hash_levels* lv, const float* sigma_w,
                      const float* rgb_w, int n, float* sigmas /*[n]*/, float* rgbs /*[n,3]*/, float* enc_out, void* stream);
 
+/* A whole image of the deployment model in ONE launch: per ray the slab test of ngp_ray_aabb (scale 0.5, near plane 0.01), the sample
+ * sequence of ngp_march_train with zero noise on one 128^3 cascade at exp_step_factor 0 (at most max_samples samples), the shading of
+ * ngp_deploy_shade at xyz = o + t d, and the serial front-to-back composite of ngp_composite_train_fwd over black: before each sample
+ * stop unless T > T_threshold; a = 1 - exp(-sigma dt), w = a T, rgb += w c, depth += w t, opacity += w, T *= 1 - a.  The march of a
+ * ray ends with its composite: nothing behind the termination point is marched or shaded.  rays_o, rays_d: [n_rays,3] (ngp_get_rays);
+ * density_bitfield: the 262 144 bytes of the cascade; coarse (nullable): ngp_bitfield_coarsen of it, 128 words, built once per model;
+ * table, lv, sigma_w, rgb_w: as for ngp_deploy_shade.  Outputs, every ray written (a miss: zeros): rgb [n_rays,3], opacity, depth
+ * [n_rays], n_samples [n_rays] int32 = composited samples, t_last [n_rays] = t of the last composited sample (0 if none).  Every output
+ * is a function of its ray alone (no atomics, no dependence on launch geometry or ray order); no per-sample data is written, nothing
+ * is allocated or read back.  A ray with an all-zero direction is a miss.  -1 without a launch: a null pointer other than coarse, a
+ * level table that is not ngp_deploy_shade's, a table not 16-byte aligned, max_samples < 1. */
+int ngp_deploy_render(const float* rays_o, const float* rays_d, const uint8_t* density_bitfield, const uint32_t* coarse /* may be NULL */,
+                      const float* table, const ngp_hash_levels* lv, const float* sigma_w, const float* rgb_w, int n_rays,
+                      int max_samples, float T_threshold, float* rgb, float* opacity, float* depth, int32_t* n_samples, float* t_last,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

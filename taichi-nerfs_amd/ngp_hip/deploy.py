@@ -10,7 +10,8 @@ written by this package: `deployment.npy` (modules.utils.save_deployment_model) 
     out = m.render(m.poses[20], res=(300, 600))          # {'rgb', 'opacity', 'depth', 'total_samples'}
 
 Loading and validation are host-side numpy; shading and rendering need the GPU (there is no CPU path).  Rays are marched and
-composited by the package's existing kernels; the shading between them is ngp_deploy_shade (csrc/deploy.hip), fp32 throughout."""
+composited by the package's existing kernels; the shading between them is ngp_deploy_shade (csrc/deploy.hip), fp32 throughout.
+render(..., mode="fused") does all of it per ray in one launch instead (ngp_deploy_render)."""
 import os
 
 import numpy as np
@@ -73,6 +74,7 @@ class DeployedModel:
         self.poses = None if poses is None else np.asarray(poses, np.float32).reshape(-1, 3, 4)
         self.device = torch.device(device) if device is not None else None
         self._dev = None
+        self._coarse = None
 
     # ------------------------------------------------------------------------------------------ loaders
     @classmethod
@@ -147,6 +149,12 @@ class DeployedModel:
             self.device = dev
         return self._dev
 
+    def _coarse_table(self):
+        """The coarse 8^3-block occupancy bits of the fused renderer's march, built once per model on first use."""
+        if self._coarse is None:
+            self._coarse = ops.coarse_bitfield(self._tensors()[3], CASCADES, GRID_SIZE)
+        return self._coarse
+
     def shade(self, xyzs, dirs, return_enc=False):
         """World positions [n,3] in [-0.5, 0.5], directions [n,3] -> (sigmas [n], rgbs [n,3]) (+ the [n,16] embedding)."""
         table, sw, rw, _ = self._tensors()
@@ -159,19 +167,27 @@ class DeployedModel:
         mode="oneshot": every ray is marched to the end of the box (at most max_samples occupied steps, default 1024), shaded and
         composited front to back until T <= T_threshold.  mode="progressive": the reference's rounds -- every alive ray advances by
         N_samples = max(min(N_rays // N_alive, 64), 1) occupied steps per round until the summed round budgets reach max_samples
-        (default 100); rays still alive then keep what they have accumulated.
+        (default 100); rays still alive then keep what they have accumulated.  mode="fused": one-shot's image from ONE launch behind
+        get_rays -- every ray is marched, shaded and composited by its own lane and its march ends where its composite does (at most
+        max_samples composited samples, default 1024); no per-sample arrays, no chunk loop, no host read.
         -> {'rgb': [N,3], 'opacity': [N], 'depth': [N], 'total_samples': int64 tensor} on the device; progressive mode adds 'schedule'
-        (the (N_alive, N_samples) of every round) and 'alive' (the rays the budget ran out on)."""
-        if mode not in ("oneshot", "progressive"):
-            raise ValueError("mode must be 'oneshot' or 'progressive', got %r" % (mode,))
+        (the (N_alive, N_samples) of every round) and 'alive' (the rays the budget ran out on), fused mode 'n_samples' ([N] int32, the
+        composited samples of every ray; one-shot counts the same samples in total_samples)."""
+        if mode not in ("oneshot", "progressive", "fused"):
+            raise ValueError("mode must be 'oneshot', 'progressive' or 'fused', got %r" % (mode,))
         _, _, _, bits = self._tensors()
         dev = self.device
         if directions is None:
             directions = get_directions(res[0], res[1], camera_angle_x)
         directions = torch.as_tensor(directions, dtype=torch.float32).reshape(-1, 3).to(dev).contiguous()
-        pose = torch.as_tensor(np.asarray(pose.detach().cpu() if torch.is_tensor(pose) else pose, np.float32).reshape(3, 4)).to(dev)
+        if torch.is_tensor(pose):
+            pose = pose.detach().to(dev, torch.float32).reshape(3, 4)      # a device pose stays there: no host read in front of the frame
+        else:
+            pose = torch.as_tensor(np.asarray(pose, np.float32).reshape(3, 4)).to(dev)
         from .rays import get_rays
         rays_o, rays_d = get_rays(directions, pose)            # rays_d = directions @ pose[:, :3].T (k = 0, 1, 2 in order), origin pose[:, 3]
+        if mode == "fused":
+            return self._render_fused(rays_o, rays_d, bits, T_threshold, 1024 if max_samples is None else int(max_samples))
         hits_t = ops.ray_aabb(rays_o, rays_d, SCALE)           # the slab test of modules/intersection.py, near plane 0.01
         if mode == "progressive":
             return self._render_progressive(rays_o, rays_d, hits_t, bits, T_threshold, 100 if max_samples is None else int(max_samples))
@@ -193,6 +209,12 @@ class DeployedModel:
             opacity[a:b] = op_c; depth[a:b] = dep_c; rgb[a:b] = rgb_c
             total += vr.sum()
         return {'rgb': rgb, 'opacity': opacity, 'depth': depth, 'total_samples': total}
+
+    def _render_fused(self, rays_o, rays_d, bits, T_threshold, max_samples):
+        table, sw, rw, _ = self._tensors()
+        rgb, opacity, depth, n_samples, _ = ops.deploy_render(rays_o, rays_d, bits, self._coarse_table(), table, self.levels, sw, rw,
+                                                              T_threshold, max_samples)
+        return {'rgb': rgb, 'opacity': opacity, 'depth': depth, 'total_samples': n_samples.sum(dtype=torch.int64), 'n_samples': n_samples}
 
     def _render_progressive(self, rays_o, rays_d, hits_t, bits, T_threshold, max_samples):
         n, dev = rays_o.shape[0], rays_o.device

@@ -17,7 +17,7 @@ INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
 LIB_PATH = os.path.join(CSRC, "libngp_hip.so")
 SOURCES = ["march.hip", "hash_grid.hip", "hash_bwd_lds.hip", "composite.hip", "sh_grid.hip", "mlp.hip", "optim.hip", "distortion.hip", "occupancy.hip", "rays.hip",
            "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip"]
-HEADERS = ["ngp_device.h", "hash_common.h"]
+HEADERS = ["ngp_device.h", "hash_common.h", "march_common.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 FLAGS_STAMP = LIB_PATH + ".flags"      # the flags the in-tree .so was built with: a flag change rebuilds
 
@@ -203,6 +203,7 @@ SIGNATURES = {
     "ngp_voxel_occ_scratch_doubles": [],
     "ngp_voxel_occ_pack": [_P, ctypes.c_longlong, ctypes.c_double, _P, _P, _P],
     "ngp_deploy_shade": [_P, _P, _P, _LV, _P, _P, _I, _P, _P, _P, _P],
+    "ngp_deploy_render": [_P, _P, _P, _P, _P, _LV, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P],
     "ngp_sh16_fwd": [_P, _I, _P, _P],
     "ngp_sh16_bwd": [_P, _P, _I, _P, _P],
     "ngp_composite_train_fwd": [_P, _P, _I, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P],

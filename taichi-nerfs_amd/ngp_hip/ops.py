@@ -460,6 +460,45 @@ def deploy_shade(xyzs, dirs, table, lv, sigma_w, rgb_w, return_enc=False):
     return (sigmas, rgbs, enc) if return_enc else (sigmas, rgbs)
 
 
+def deploy_render(rays_o, rays_d, density_bitfield, coarse, table, lv, sigma_w, rgb_w, T_threshold=1e-2, max_samples=1024, out=None):
+    """Rays of a deployment model to pixels in one launch (ngp_deploy_render): slab test, occupancy march, shading and front-to-back
+    compositing per ray, the march ending where the composite does.  rays_o, rays_d [n,3] f32; density_bitfield: the 262 144 uint8 of the
+    one 128^3 cascade; coarse: coarse_bitfield(density_bitfield, 1, 128) (int32 [128]) or None; table, lv, sigma_w, rgb_w as for
+    deploy_shade.  -> (rgb [n,3], opacity [n], depth [n], n_samples [n] int32, t_last [n]); `out` = that tuple preallocated.
+    Shapes and dtypes are checked first (ValueError), then that everything lives on the GPU."""
+    f32, n = torch.float32, rays_o.shape[0]
+    want = [(rays_o, "rays_o", f32, (n, 3)), (rays_d, "rays_d", f32, (n, 3)), (table, "hash_table", f32, (lv.total_entries * 4,)),
+            (sigma_w, "sigma_weights", f32, (512,)), (rgb_w, "rgb_weights", f32, (768,)),
+            (density_bitfield, "density_bitfield", torch.uint8, (128**3 // 8,))]
+    if coarse is not None:
+        want.append((coarse, "coarse", torch.int32, (128**3 // 512 // 32,)))          # coarse_bitfield(density_bitfield, 1, 128)
+    if out is not None:
+        rgb, opacity, depth, n_samples, t_last = out
+        want += [(rgb, "out rgb", f32, (n, 3)), (opacity, "out opacity", f32, (n,)), (depth, "out depth", f32, (n,)),
+                 (n_samples, "out n_samples", torch.int32, (n,)), (t_last, "out t_last", f32, (n,))]
+    if lv.n_levels != 4 or lv.n_features != 4 or lv.begin_fast_hash_level != 4:
+        raise ValueError("deploy_render needs the deployment level table: 4 dense levels of 4 features")
+    for t, name, dt, shape in want:
+        if t.dtype != dt or tuple(t.shape) != shape:
+            raise ValueError("deploy_render: %s must be %s %s, got %s %s" % (name, dt, shape, t.dtype, tuple(t.shape)))
+    if table.data_ptr() % 16:
+        raise ValueError("deploy_render: the hash table must be 16-byte aligned")
+    if int(max_samples) < 1:
+        raise ValueError("deploy_render: max_samples must be at least 1, got %r" % (max_samples,))
+    for t, name, dt, _ in want:
+        _dev(t, dt, name)
+    if out is None:
+        dev = rays_o.device
+        out = (torch.empty(n, 3, device=dev), torch.empty(n, device=dev), torch.empty(n, device=dev),
+               torch.empty(n, device=dev, dtype=torch.int32), torch.empty(n, device=dev))
+    rgb, opacity, depth, n_samples, t_last = out
+    check(_lib().ngp_deploy_render(_ptr(rays_o), _ptr(rays_d), _ptr(density_bitfield), _ptr(coarse), _ptr(table), ctypes.byref(lv),
+                                   _ptr(sigma_w), _ptr(rgb_w), n, int(max_samples), float(T_threshold), _ptr(rgb), _ptr(opacity), _ptr(depth),
+                                   _ptr(n_samples), _ptr(t_last), _stream()), "ngp_deploy_render")
+    _touched(*out)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- a-6
 def sh16_fwd(dirs):
     _dev(dirs, torch.float32, "dirs")
