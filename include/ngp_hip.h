@@ -145,6 +145,28 @@ int ngp_hash_fwd_f32(const float* xyzs /*[n,3] in [0,1]*/, const float* table,
 int ngp_hash_bwd_f32(const float* xyzs, const float* dout /*[n, L*F]*/,
                      const ngp_hash_levels* lv, int n, float* dtable, void* stream);
 
+/* ---- a-4x  gradient of the encoding with respect to the sample POSITION (csrc/hash_grad_input.hip; not in the reference, whose
+ * backward returns None for the positions, hash_encoder.py:277).  dxyzs [n,3] is WRITTEN, every element, never accumulated:
+ *   dx_k = sum_l scale_l * sum_f denc[l,f] * sum_c s_k(c) * prod_{j != k} w_j(c) * T[off_l + idx_c, f]
+ * with s_k(c) = +1 where corner c lies on the far side along axis k and -1 otherwise, w_j(c) = fr_j on the far side and 1 - fr_j
+ * otherwise: the derivative of the forward as the forward evaluates it (its f32 cell and fraction, d fr / d pos = 1).
+ * Face rule: on a cell face (fr == 0) it is the derivative of the cell floorf selects, i.e. the one-sided derivative towards larger
+ * coordinates.  Positions outside [0, 1] and NaN positions take the cell the forward gives them; no read leaves the table (a NaN
+ * position yields a NaN row and touches no other row).  Products and sums are f32; the sum over levels is a fixed shuffle tree (no
+ * atomics): two runs on the same input are bit-identical.  denc is the natural [n, L*F] layout.  n == 0 returns 0 without a launch.
+ * Once differentiable: the gradient of dx with respect to the table (a double backward) is not provided.
+ * ngp_hash_bwd_input_f32 differentiates ngp_hash_fwd_f32: same (L, F) domain (1 <= L <= 16, F in {1, 2, 4, 8}), -1 outside it. */
+int ngp_hash_bwd_input_f32 (const float* xyzs, const float* table, const float* denc /*[n, L*F]*/, const ngp_hash_levels* lv, int n,
+                            float* dxyzs /*[n,3]*/, void* stream);
+/* Differentiates ngp_hash_fwd_bf16_ex (normalize = 0, natural layout): the bf16 storage copy the forward read (F = 2), widened
+ * exactly; same face rule.  Equals ngp_hash_bwd_input_f32 on the bf16-rounded table, bit for bit. */
+int ngp_hash_bwd_input_bf16(const float* xyzs, const uint16_t* table, const float* denc /*[n, L*2]*/, const ngp_hash_levels* lv, int n,
+                            float* dxyzs /*[n,3]*/, void* stream);
+/* Differentiates ngp_hash_fwd_f16 (the half2 encoder, F = 2): f16 table entries and f16 denc, widened exactly, and the forward's
+ * f16-rounded cell in the fraction; same face rule.  The forward's f16 roundings of its products and sums are not differentiated. */
+int ngp_hash_bwd_input_f16 (const float* xyzs, const uint16_t* table, const uint16_t* denc /*[n,L,2] f16*/, const ngp_hash_levels* lv,
+                            int n, float* dxyzs /*[n,3]*/, void* stream);
+
 /* Sync-free forms used by the fused training step: the sample count is read ON THE DEVICE from n_dev[0] (the
  * `total` written by ngp_march_train_scan; NULL = use n_max), buffers are sized for n_max, and `normalize` fuses the
  * caller-side position normalisation (x - lo) / (hi - lo) of modules/networks.py:144 (same two f32 operations).

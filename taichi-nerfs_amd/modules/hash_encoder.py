@@ -2,8 +2,14 @@
 
 The forward gather and the scatter-add backward are the gfx950 kernels ngp_hash_fwd_f32 / ngp_hash_bwd_f32.
 The backward is the TRUE gradient of the forward w.r.t. the table (the reference hands autograd a tensor that
-torch then adds to itself, i.e. 2x the gradient -- SURVEY.md H7; Adam is invariant to that factor)."""
+torch then adds to itself, i.e. 2x the gradient -- SURVEY.md H7; Adam is invariant to that factor).
+
+Positions that require grad also receive one (ngp_hash_bwd_input_f32 / _bf16; the reference returns None, :277): the derivative of the
+forward as it evaluates -- its f32 cell and fraction, and on a cell face the cell floorf selects.  The backwards are ONCE
+differentiable: the gradient of that position gradient w.r.t. the table (a double backward) is not provided.  Positions that do not
+require grad launch nothing new."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from ngp_hip import ops as _ops
 from .utils import scale_in_level_np
@@ -14,16 +20,25 @@ class _HashEncodeF32(torch.autograd.Function):
     @staticmethod
     def forward(ctx, positions, table, levels):
         ctx.levels = levels
-        ctx.save_for_backward(positions)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(positions, table)              # d enc / d positions reads the table the forward read
+        else:
+            ctx.save_for_backward(positions)
         ctx.table_numel = table.numel()
         return _ops.hash_fwd_f32(positions, table, levels)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
-        (positions,) = ctx.saved_tensors
-        dtable = torch.zeros(ctx.table_numel, device=dout.device, dtype=torch.float32)
-        _ops.hash_bwd_f32(positions, dout.contiguous().float(), ctx.levels, dtable)
-        return None, dtable, None
+        positions = ctx.saved_tensors[0]
+        dout = dout.contiguous().float()
+        dx = dtable = None
+        if ctx.needs_input_grad[0]:
+            dx = _ops.hash_bwd_input_f32(positions, ctx.saved_tensors[1], dout, ctx.levels)
+        if ctx.needs_input_grad[1]:
+            dtable = torch.zeros(ctx.table_numel, device=dout.device, dtype=torch.float32)
+            _ops.hash_bwd_f32(positions, dout, ctx.levels, dtable)
+        return dx, dtable, None
 
 
 class _HashEncodeBF16(torch.autograd.Function):
@@ -33,16 +48,25 @@ class _HashEncodeBF16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, positions, table, table_bf16, levels):
         ctx.levels = levels
-        ctx.save_for_backward(positions)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(positions, table_bf16)         # the copy the forward read, not the fp32 master
+        else:
+            ctx.save_for_backward(positions)
         ctx.table_numel = table.numel()
         return _ops.hash_fwd_bf16(positions, table_bf16, levels)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
-        (positions,) = ctx.saved_tensors
-        dtable = torch.zeros(ctx.table_numel, device=dout.device, dtype=torch.float32)
-        _ops.hash_bwd_f32(positions, dout.contiguous().float(), ctx.levels, dtable)
-        return None, dtable, None, None
+        positions = ctx.saved_tensors[0]
+        dout = dout.contiguous().float()
+        dx = dtable = None
+        if ctx.needs_input_grad[0]:
+            dx = _ops.hash_bwd_input_bf16(positions, ctx.saved_tensors[1], dout, ctx.levels)
+        if ctx.needs_input_grad[1]:
+            dtable = torch.zeros(ctx.table_numel, device=dout.device, dtype=torch.float32)
+            _ops.hash_bwd_f32(positions, dout, ctx.levels, dtable)
+        return dx, dtable, None, None
 
 
 class HashEncoder(torch.nn.Module):

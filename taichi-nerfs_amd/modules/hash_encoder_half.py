@@ -3,8 +3,14 @@
 fp32 master table [entries, F] -> fp16 copy per forward (:367); f16 gather with f16 accumulation
 (ngp_hash_fwd_f16); explicit backward with one packed f16x2 atomic per corner (ngp_hash_bwd_f16,
 global_atomic_pk_add_f16).  The gradient buffer is a genuine fp16 buffer (the reference binds an fp32 tensor to
-an f16-typed ndarray) and is returned to autograd as fp32 like the parameter."""
+an f16-typed ndarray) and is returned to autograd as fp32 like the parameter.
+
+Positions that require grad also receive one (ngp_hash_bwd_input_f16; the reference returns None): f32 arithmetic on the fp16 table
+copy and the f16-rounded cell the forward used, and on a cell face the cell floorf selects; the forward's f16 roundings of its
+products are not differentiated.  The backward is ONCE differentiable: the gradient of that position gradient w.r.t. the table (a
+double backward) is not provided.  Positions that do not require grad launch nothing new."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from ngp_hip import ops as _ops
 from .utils import scale_in_level_np
@@ -15,17 +21,26 @@ class _HashEncodeF16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, positions, table_h, module):
         ctx.module = module
-        ctx.save_for_backward(positions)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(positions, table_h)                    # d enc / d positions reads the fp16 copy the forward read
+        else:
+            ctx.save_for_backward(positions)
         return _ops.hash_fwd_f16(positions, table_h, module._levels)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
-        (positions,) = ctx.saved_tensors
+        positions = ctx.saved_tensors[0]
         m = ctx.module
-        grad_h = m._grad_f16(dout.device)
-        grad_h.zero_()                                                   # reference :350-352
-        _ops.hash_bwd_f16(positions, dout.contiguous().to(torch.float16), m._levels, grad_h)
-        return None, grad_h, None
+        dout = dout.contiguous().to(torch.float16)
+        dx = grad_h = None
+        if ctx.needs_input_grad[0]:
+            dx = _ops.hash_bwd_input_f16(positions, ctx.saved_tensors[1], dout, m._levels)
+        if ctx.needs_input_grad[1]:
+            grad_h = m._grad_f16(dout.device)
+            grad_h.zero_()                                               # reference :350-352
+            _ops.hash_bwd_f16(positions, dout, m._levels, grad_h)
+        return dx, grad_h, None
 
 
 class HashEncoder(torch.nn.Module):

@@ -182,6 +182,26 @@ class NGP(nn.Module):
         rgbs = self.rgb_net(torch.cat([sh, h], 1))
         return sigmas, rgbs
 
+    def density_normals(self, x, eps=1e-20):
+        """x: [N,3] in [-scale, scale] -> (sigmas [N], normals [N,3], grad [N,3]): grad = d sigma / d x from one torch.autograd.grad
+        through self.density (the hash encoder's position gradient, ngp_hash_bwd_input_*), normals = -grad / max(|grad|, eps).
+
+        Runs under torch.enable_grad() on a detached copy of x, so it works inside torch.no_grad() evaluation, and writes no
+        parameter .grad.  The gradient is that of the density as the encoder evaluates it: piecewise constant per grid cell along
+        each axis and, on a cell face, that of the cell the forward selects.  Once differentiable: the result carries no graph (no
+        loss on normals trains the table through it).  Where the parameters require grad, the backward still forms their gradients
+        and autograd drops them; freeze the model (requires_grad_(False)) to skip that work.  Tri-plane models raise
+        NotImplementedError."""
+        if self.pos_encoder_type != 'hash':
+            raise NotImplementedError("density_normals needs the hash encoder's position gradient; pos_encoder_type=%r has none yet"
+                                      % (self.pos_encoder_type,))
+        with torch.enable_grad():
+            xg = x.detach().clone().requires_grad_(True)
+            sigmas = self.density(xg)
+            (grad,) = torch.autograd.grad(sigmas.sum(), xg)
+        normals = -grad / torch.linalg.norm(grad, dim=1, keepdim=True).clamp_min(eps)
+        return sigmas.detach(), normals, grad
+
     # ------------------------------------------------------------------------------------------ occupancy grid
     @torch.no_grad()
     def get_all_cells(self):
@@ -414,6 +434,10 @@ class VoxelGrid(nn.Module):
             return self.forward(x, torch.ones_like(x))[0]
         return _ops.voxel_density(x, self.density_fields, self.grid_size, self.grid_min, float(self.grid_radius),
                                   trilinear=self.use_trilinear)
+
+    def density_normals(self, x, eps=1e-20):
+        """NGP.density_normals is not available here: the voxel-grid lookup has no position gradient yet."""
+        raise NotImplementedError("density_normals needs a position gradient; the voxel-grid model (svox) has none yet")
 
     # ------------------------------------------------------------------------------------------ occupancy grid
     get_all_cells = NGP.get_all_cells

@@ -324,6 +324,39 @@ def hash_bwd_f16_sliced(xyzs, dout, lv, dtable_h, live_idx=None, n_dev=None):
     return dtable_h
 
 
+# ---------------------------------------------------------------------------------------------------- a-4x
+def _hash_bwd_input(entry, xyzs, table, table_dtype, denc, denc_dtype, lv):
+    _dev(xyzs, torch.float32, "xyzs"); _dev(table, table_dtype, "hash_table"); _dev(denc, denc_dtype, "denc")
+    n = xyzs.shape[0]
+    if xyzs.numel() != 3 * n:
+        raise ValueError("xyzs must be [n, 3], got %s" % (tuple(xyzs.shape),))
+    if table.numel() != lv.total_entries * lv.n_features:
+        raise ValueError("hash_table has %d elements, the level table describes %d" % (table.numel(), lv.total_entries * lv.n_features))
+    if denc.numel() != n * lv.n_levels * lv.n_features:
+        raise ValueError("denc must hold [n, levels * features] = %d x %d values, got %s"
+                         % (n, lv.n_levels * lv.n_features, tuple(denc.shape)))
+    dxyzs = torch.empty(n, 3, device=xyzs.device, dtype=torch.float32)
+    check(getattr(_lib(), entry)(_ptr(xyzs), _ptr(table), _ptr(denc), ctypes.byref(lv), n, _ptr(dxyzs), _stream()), entry)
+    return dxyzs
+
+
+def hash_bwd_input_f32(xyzs, table, denc, lv):
+    """d(loss)/d(xyzs) [n,3] of hash_fwd_f32 for d(loss)/d(encoding) = denc [n, L*F]: the derivative of the forward as it evaluates
+    (its cell and fraction; on a cell face the cell floorf selects).  Written, not accumulated; bit-reproducible; once differentiable."""
+    return _hash_bwd_input("ngp_hash_bwd_input_f32", xyzs, table, torch.float32, denc, torch.float32, lv)
+
+
+def hash_bwd_input_bf16(xyzs, table_bf16, denc, lv):
+    """hash_bwd_input_f32 for hash_fwd_bf16: table_bf16 is the bf16 storage copy the forward gathered from (F = 2)."""
+    return _hash_bwd_input("ngp_hash_bwd_input_bf16", xyzs, table_bf16, torch.bfloat16, denc, torch.float32, lv)
+
+
+def hash_bwd_input_f16(xyzs, table_h, denc_h, lv):
+    """hash_bwd_input_f32 for the half2 encoder (hash_fwd_f16): fp16 table [entries, 2], fp16 denc [n, L, 2], f32 arithmetic on the
+    forward's f16-rounded cell."""
+    return _hash_bwd_input("ngp_hash_bwd_input_f16", xyzs, table_h, torch.float16, denc_h, torch.float16, lv)
+
+
 # ---------------------------------------------------------------------------------------------------- a-4t
 def make_triplane_levels(base_res, max_res, levels, features):
     """ngp_triplane_levels table (host struct) -- TriPlaneEncoder.__init__ arithmetic (triplane.py:103-160)."""
