@@ -154,7 +154,7 @@ int ngp_hash_bwd_f32(const float* xyzs, const float* dout /*[n, L*F]*/,
  * coordinates.  Positions outside [0, 1] and NaN positions take the cell the forward gives them; no read leaves the table (a NaN
  * position yields a NaN row and touches no other row).  Products and sums are f32; the sum over levels is a fixed shuffle tree (no
  * atomics): two runs on the same input are bit-identical.  denc is the natural [n, L*F] layout.  n == 0 returns 0 without a launch.
- * Once differentiable: the gradient of dx with respect to the table (a double backward) is not provided.
+ * These entries are first order; the double backward through dx is ngp_hash_bwd2_* below.
  * ngp_hash_bwd_input_f32 differentiates ngp_hash_fwd_f32: same (L, F) domain (1 <= L <= 16, F in {1, 2, 4, 8}), -1 outside it. */
 int ngp_hash_bwd_input_f32 (const float* xyzs, const float* table, const float* denc /*[n, L*F]*/, const ngp_hash_levels* lv, int n,
                             float* dxyzs /*[n,3]*/, void* stream);
@@ -166,6 +166,28 @@ int ngp_hash_bwd_input_bf16(const float* xyzs, const uint16_t* table, const floa
  * f16-rounded cell in the fraction; same face rule.  The forward's f16 roundings of its products and sums are not differentiated. */
 int ngp_hash_bwd_input_f16 (const float* xyzs, const uint16_t* table, const uint16_t* denc /*[n,L,2] f16*/, const ngp_hash_levels* lv,
                             int n, float* dxyzs /*[n,3]*/, void* stream);
+
+/* ---- a-4xx  double backward through dxyzs (csrc/hash_grad_input2.hip): for ddx [n,3] the gradient of a loss with respect to the dxyzs
+ * of ngp_hash_bwd_input_*, and A_c = sum_k ddx_k * s_k(c) * prod_{j != k} w_j(c),
+ *   d_denc[l,f]            = scale_l * sum_c A_c * T[off_l + idx_c, f]
+ *   d_xyzs[m]              = sum_l scale_l^2 * sum_{k != m} ddx_k * M_km,
+ *                            M_km = sum_b w_j(b) * (t[1_k,1_m,b] - t[0_k,1_m,b] - t[1_k,0_m,b] + t[0_k,0_m,b]),  t_c = denc[l,:] . T_c
+ *   dtable[off_l + idx_c,f] += scale_l * A_c * denc[l,f]
+ * (j the third axis; the diagonal M_kk is exactly 0).  Same cell, fraction, face rule and (L, F) domain as the first backward; no
+ * access leaves the table for any input.  The gather entries WRITE d_denc [n, L*F] and d_xyzs [n,3], every element, without atomics
+ * (bit-identical from run to run); either pointer may be NULL and that output is skipped.  ngp_hash_bwd2_gather_bf16 reads the bf16
+ * storage copy (F = 2) and equals the f32 entry on the bf16-rounded table bit for bit.  ngp_hash_bwd2_table_f32 ACCUMULATES into
+ * dtable with float atomics like ngp_hash_bwd_f32 (summation order not deterministic) and skips contributions that are exactly 0;
+ * it does not read the table, so it serves both encoders (the bf16-copy encoder's gradient goes to the fp32 master).
+ * n <= 0 returns 0 without a launch; an (L, F) outside the forward's domain returns -1. */
+int ngp_hash_bwd2_gather_f32 (const float* xyzs, const float* table, const float* denc /*[n, L*F]*/, const float* ddx /*[n,3]*/,
+                              const ngp_hash_levels* lv, int n, float* d_denc /*[n, L*F] or NULL*/, float* d_xyzs /*[n,3] or NULL*/,
+                              void* stream);
+int ngp_hash_bwd2_gather_bf16(const float* xyzs, const uint16_t* table, const float* denc /*[n, L*2]*/, const float* ddx /*[n,3]*/,
+                              const ngp_hash_levels* lv, int n, float* d_denc /*[n, L*2] or NULL*/, float* d_xyzs /*[n,3] or NULL*/,
+                              void* stream);
+int ngp_hash_bwd2_table_f32  (const float* xyzs, const float* denc /*[n, L*F]*/, const float* ddx /*[n,3]*/, const ngp_hash_levels* lv,
+                              int n, float* dtable /* += */, void* stream);
 
 /* Sync-free forms used by the fused training step: the sample count is read ON THE DEVICE from n_dev[0] (the
  * `total` written by ngp_march_train_scan; NULL = use n_max), buffers are sized for n_max, and `normalize` fuses the

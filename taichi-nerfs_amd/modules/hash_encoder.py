@@ -5,9 +5,14 @@ The backward is the TRUE gradient of the forward w.r.t. the table (the reference
 torch then adds to itself, i.e. 2x the gradient -- SURVEY.md H7; Adam is invariant to that factor).
 
 Positions that require grad also receive one (ngp_hash_bwd_input_f32 / _bf16; the reference returns None, :277): the derivative of the
-forward as it evaluates -- its f32 cell and fraction, and on a cell face the cell floorf selects.  The backwards are ONCE
-differentiable: the gradient of that position gradient w.r.t. the table (a double backward) is not provided.  Positions that do not
-require grad launch nothing new."""
+forward as it evaluates -- its f32 cell and fraction, and on a cell face the cell floorf selects.  By default the backwards are ONCE
+differentiable.  Positions that do not require grad launch nothing new.
+
+HashEncoder(twice_differentiable=True) selects Functions whose backward is itself an autograd Function (_HashGradF32 / _HashGradBF16):
+torch.autograd.grad(..., create_graph=True) then returns a position gradient that carries a graph, and a loss on it (eikonal, normal
+smoothness, gradient penalty) trains the table, the layers that produced the incoming gradient and the positions through
+ngp_hash_bwd2_gather_* / ngp_hash_bwd2_table_f32 (csrc/hash_grad_input2.hip).  First-order results have the default path's bits.
+The table gradient itself is marked non-differentiable: differentiating THROUGH it raises instead of returning something wrong."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -69,16 +74,132 @@ class _HashEncodeBF16(torch.autograd.Function):
         return dx, dtable, None, None
 
 
+class _HashGradF32(torch.autograd.Function):
+    """The first backward of the fp32 encoder as a differentiable function of (dout, positions, table): (dx | None, dtable | None) by
+    the operators the default path calls.  Its own backward (for ddx = d loss / d dx) is the double backward; dtable is not
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, dout, positions, table, levels, need_x, need_table):
+        ctx.levels, ctx.dout_dtype = levels, dout.dtype
+        ctx.set_materialize_grads(False)
+        d = dout.contiguous().float()
+        dx = dtable = None
+        if need_x:
+            dx = _ops.hash_bwd_input_f32(positions, table, d, levels)
+            ctx.save_for_backward(d, positions, table)
+        if need_table:
+            dtable = torch.zeros(table.numel(), device=d.device, dtype=torch.float32)
+            _ops.hash_bwd_f32(positions, d, levels, dtable)
+            ctx.mark_non_differentiable(dtable)
+        return dx, dtable
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ddx, _ddtable):
+        if ddx is None:
+            return None, None, None, None, None, None
+        d, positions, table = ctx.saved_tensors
+        ddx = ddx.contiguous().float()
+        need = ctx.needs_input_grad
+        d_denc = d_x = d_table = None
+        if need[0] or need[1]:
+            d_denc, d_x = _ops.hash_bwd2_gather_f32(positions, table, d, ddx, ctx.levels, need_denc=need[0], need_x=need[1])
+            if d_denc is not None:
+                d_denc = d_denc.to(ctx.dout_dtype)
+        if need[2]:
+            d_table = torch.zeros(table.numel(), device=d.device, dtype=torch.float32)
+            _ops.hash_bwd2_table_f32(positions, d, ddx, ctx.levels, d_table)
+            d_table = d_table.view(table.shape)
+        return d_denc, d_x, d_table, None, None, None
+
+
+class _HashGradBF16(torch.autograd.Function):
+    """_HashGradF32 for the bf16-copy encoder: dx and its double backward read the bf16 copy the forward read; both table gradients go
+    to the fp32 master (neither scatter reads the table)."""
+
+    @staticmethod
+    def forward(ctx, dout, positions, table, table_bf16, levels, need_x, need_table):
+        ctx.levels, ctx.dout_dtype, ctx.table_shape = levels, dout.dtype, table.shape
+        ctx.set_materialize_grads(False)
+        d = dout.contiguous().float()
+        dx = dtable = None
+        if need_x:
+            dx = _ops.hash_bwd_input_bf16(positions, table_bf16, d, levels)
+            ctx.save_for_backward(d, positions, table_bf16)
+        if need_table:
+            dtable = torch.zeros(table.numel(), device=d.device, dtype=torch.float32)
+            _ops.hash_bwd_f32(positions, d, levels, dtable)
+            ctx.mark_non_differentiable(dtable)
+        return dx, dtable
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ddx, _ddtable):
+        if ddx is None:
+            return None, None, None, None, None, None, None
+        d, positions, table_bf16 = ctx.saved_tensors
+        ddx = ddx.contiguous().float()
+        need = ctx.needs_input_grad
+        d_denc = d_x = d_table = None
+        if need[0] or need[1]:
+            d_denc, d_x = _ops.hash_bwd2_gather_bf16(positions, table_bf16, d, ddx, ctx.levels, need_denc=need[0], need_x=need[1])
+            if d_denc is not None:
+                d_denc = d_denc.to(ctx.dout_dtype)
+        if need[2]:
+            d_table = torch.zeros(table_bf16.numel(), device=d.device, dtype=torch.float32)
+            _ops.hash_bwd2_table_f32(positions, d, ddx, ctx.levels, d_table)
+            d_table = d_table.view(ctx.table_shape)
+        return d_denc, d_x, d_table, None, None, None, None
+
+
+class _HashEncodeF32Twice(torch.autograd.Function):
+    """_HashEncodeF32 whose backward is _HashGradF32: differentiable once more."""
+
+    @staticmethod
+    def forward(ctx, positions, table, levels):
+        ctx.levels = levels
+        ctx.save_for_backward(positions, table)
+        return _ops.hash_fwd_f32(positions, table, levels)
+
+    @staticmethod
+    def backward(ctx, dout):
+        positions, table = ctx.saved_tensors
+        dx, dtable = _HashGradF32.apply(dout, positions, table, ctx.levels, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return dx, dtable, None
+
+
+class _HashEncodeBF16Twice(torch.autograd.Function):
+    """_HashEncodeBF16 whose backward is _HashGradBF16: differentiable once more."""
+
+    @staticmethod
+    def forward(ctx, positions, table, table_bf16, levels):
+        ctx.levels = levels
+        ctx.save_for_backward(positions, table, table_bf16)
+        return _ops.hash_fwd_bf16(positions, table_bf16, levels)
+
+    @staticmethod
+    def backward(ctx, dout):
+        positions, table, table_bf16 = ctx.saved_tensors
+        dx, dtable = _HashGradBF16.apply(dout, positions, table, table_bf16, ctx.levels, ctx.needs_input_grad[0],
+                                         ctx.needs_input_grad[1])
+        return dx, dtable, None, None
+
+
 class HashEncoder(torch.nn.Module):
     """positions [N,3] f32 in [0,1] -> embedding [N, levels*feature_per_level] f32 (level-major).
 
     table_dtype=torch.bfloat16 (not in the reference; BASELINE config 2 names a bf16 hash grid): the forward gathers from
     a bf16 copy of the fp32 master `hash_table` (refreshed whenever the parameter changes, the way hash_encoder_half.py:367
-    re-casts its fp16 copy every call); parameter, gradient, optimizer state and state_dict stay fp32."""
+    re-casts its fp16 copy every call); parameter, gradient, optimizer state and state_dict stay fp32.
+
+    twice_differentiable=True: the position gradient can itself be differentiated (autograd.grad(..., create_graph=True) followed
+    by a backward of a loss on it); the default keeps the once-differentiable Functions."""
 
     def __init__(self, max_params: float = 2**19, levels: int = 16, base_res: float = 16.0, max_res: float = 2048.0,
-                 feature_per_level: int = 2, table_dtype=None):
+                 feature_per_level: int = 2, table_dtype=None, twice_differentiable: bool = False):
         super().__init__()
+        self.twice_differentiable = bool(twice_differentiable)
         if table_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("table_dtype must be None / torch.float32 / torch.bfloat16")
         if table_dtype == torch.bfloat16 and feature_per_level != 2:
@@ -126,5 +247,7 @@ class HashEncoder(torch.nn.Module):
 
     def forward(self, positions):
         if self.table_dtype == torch.bfloat16:
-            return _HashEncodeBF16.apply(positions.contiguous(), self.hash_table, self.table_bf16(), self._levels)
-        return _HashEncodeF32.apply(positions.contiguous(), self.hash_table.contiguous(), self._levels)
+            fn = _HashEncodeBF16Twice if self.twice_differentiable else _HashEncodeBF16
+            return fn.apply(positions.contiguous(), self.hash_table, self.table_bf16(), self._levels)
+        fn = _HashEncodeF32Twice if self.twice_differentiable else _HashEncodeF32
+        return fn.apply(positions.contiguous(), self.hash_table.contiguous(), self._levels)

@@ -93,8 +93,12 @@ class NGP(nn.Module):
     def __init__(self, scale: float = 0.5, pos_encoder_type: str = 'hash', levels: int = 16, feature_per_level: int = 2,
                  log2_T: int = 19, base_res: int = 16, max_res: int = 2048, half_opt: bool = False,
                  xyz_net_width: int = 64, xyz_net_depth: int = 1, xyz_net_out_dim: int = 16, rgb_net_depth: int = 2,
-                 rgb_net_width: int = 64, table_dtype=None):
+                 rgb_net_width: int = 64, table_dtype=None, twice_differentiable: bool = False):
         super().__init__()
+        if twice_differentiable and (half_opt or pos_encoder_type != 'hash'):
+            raise ValueError("twice_differentiable applies to the fp32 / bf16-copy hash encoder: not to half_opt=True or "
+                             "pos_encoder_type=%r" % (pos_encoder_type,))
+        self.twice_differentiable = bool(twice_differentiable)
         self.scale = scale
         self.half_opt = bool(half_opt)
         self.register_buffer('center', torch.zeros(1, 3))
@@ -120,6 +124,8 @@ class NGP(nn.Module):
                 if half_opt:
                     raise ValueError("table_dtype applies to the fp32 encoder; half_opt already selects the fp16 table")
                 enc_kw['table_dtype'] = table_dtype
+            if twice_differentiable:
+                enc_kw['twice_differentiable'] = True
             self.pos_encoder = HashEncoder(max_params=2**log2_T, base_res=base_res, max_res=max_res, levels=levels,
                                            feature_per_level=feature_per_level, **enc_kw)
         elif pos_encoder_type == 'triplane':
@@ -182,7 +188,7 @@ class NGP(nn.Module):
         rgbs = self.rgb_net(torch.cat([sh, h], 1))
         return sigmas, rgbs
 
-    def density_normals(self, x, eps=1e-20):
+    def density_normals(self, x, eps=1e-20, create_graph=False):
         """x: [N,3] in [-scale, scale] -> (sigmas [N], normals [N,3], grad [N,3]): grad = d sigma / d x from one torch.autograd.grad
         through self.density (the hash encoder's position gradient, ngp_hash_bwd_input_*), normals = -grad / max(|grad|, eps).
 
@@ -191,10 +197,23 @@ class NGP(nn.Module):
         each axis and, on a cell face, that of the cell the forward selects.  Once differentiable: the result carries no graph (no
         loss on normals trains the table through it).  Where the parameters require grad, the backward still forms their gradients
         and autograd drops them; freeze the model (requires_grad_(False)) to skip that work.  Tri-plane models raise
-        NotImplementedError."""
+        NotImplementedError.
+
+        create_graph=True (needs NGP(twice_differentiable=True), else ValueError): sigmas, normals and grad carry the graph, so a
+        loss on them trains the hash table and the xyz MLP through the encoder's double backward.  The gradient is then taken on x
+        itself where x requires grad (the loss also reaches whatever produced x), else on a detached copy."""
         if self.pos_encoder_type != 'hash':
             raise NotImplementedError("density_normals needs the hash encoder's position gradient; pos_encoder_type=%r has none yet"
                                       % (self.pos_encoder_type,))
+        if create_graph:
+            if not getattr(self.pos_encoder, 'twice_differentiable', False):
+                raise ValueError("density_normals(create_graph=True) needs a twice-differentiable encoder: NGP(twice_differentiable=True)")
+            with torch.enable_grad():
+                xg = x if x.requires_grad else x.detach().clone().requires_grad_(True)
+                sigmas = self.density(xg)
+                (grad,) = torch.autograd.grad(sigmas.sum(), xg, create_graph=True)
+                normals = -grad / torch.linalg.norm(grad, dim=1, keepdim=True).clamp_min(eps)
+            return sigmas, normals, grad
         with torch.enable_grad():
             xg = x.detach().clone().requires_grad_(True)
             sigmas = self.density(xg)

@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
 LIB_PATH = os.path.join(CSRC, "libngp_hip.so")
 SOURCES = ["march.hip", "hash_grid.hip", "hash_bwd_lds.hip", "composite.hip", "sh_grid.hip", "mlp.hip", "optim.hip", "distortion.hip", "occupancy.hip", "rays.hip",
-           "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip", "hash_grad_input.hip"]
+           "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip", "hash_grad_input.hip", "hash_grad_input2.hip"]
 HEADERS = ["ngp_device.h", "hash_common.h", "march_common.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 FLAGS_STAMP = LIB_PATH + ".flags"      # the flags the in-tree .so was built with: a flag change rebuilds
@@ -166,6 +166,9 @@ SIGNATURES = {
     "ngp_hash_bwd_input_f32": [_P, _P, _P, _LV, _I, _P, _P],
     "ngp_hash_bwd_input_bf16": [_P, _P, _P, _LV, _I, _P, _P],
     "ngp_hash_bwd_input_f16": [_P, _P, _P, _LV, _I, _P, _P],
+    "ngp_hash_bwd2_gather_f32": [_P, _P, _P, _P, _LV, _I, _P, _P, _P],
+    "ngp_hash_bwd2_gather_bf16": [_P, _P, _P, _P, _LV, _I, _P, _P, _P],
+    "ngp_hash_bwd2_table_f32": [_P, _P, _P, _LV, _I, _P, _P],
     "ngp_hash_fwd_f32_ex": [_P, _P, _LV, _I, _P, _I, _F, _F, _I, _P, _P],
     "ngp_hash_fwd_bf16_ex": [_P, _P, _LV, _I, _P, _I, _F, _F, _I, _P, _P],
     "ngp_hash_bwd_f32_ex": [_P, _P, _LV, _I, _P, _I, _F, _F, _I, _P, _P, _P],

@@ -357,6 +357,56 @@ def hash_bwd_input_f16(xyzs, table_h, denc_h, lv):
     return _hash_bwd_input("ngp_hash_bwd_input_f16", xyzs, table_h, torch.float16, denc_h, torch.float16, lv)
 
 
+# ---------------------------------------------------------------------------------------------------- a-4xx
+def _hash_bwd2_check(xyzs, denc, ddx, lv):
+    _dev(xyzs, torch.float32, "xyzs"); _dev(denc, torch.float32, "denc"); _dev(ddx, torch.float32, "ddx")
+    n = xyzs.shape[0]
+    if xyzs.numel() != 3 * n:
+        raise ValueError("xyzs must be [n, 3], got %s" % (tuple(xyzs.shape),))
+    if denc.numel() != n * lv.n_levels * lv.n_features:
+        raise ValueError("denc must hold [n, levels * features] = %d x %d values, got %s"
+                         % (n, lv.n_levels * lv.n_features, tuple(denc.shape)))
+    if ddx.numel() != 3 * n:
+        raise ValueError("ddx must be [n, 3] = [%d, 3], got %s" % (n, tuple(ddx.shape)))
+    return n
+
+
+def _hash_bwd2_gather(entry, xyzs, table, table_dtype, denc, ddx, lv, need_denc, need_x):
+    _dev(table, table_dtype, "hash_table")
+    n = _hash_bwd2_check(xyzs, denc, ddx, lv)
+    if table.numel() != lv.total_entries * lv.n_features:
+        raise ValueError("hash_table has %d elements, the level table describes %d" % (table.numel(), lv.total_entries * lv.n_features))
+    d_denc = torch.empty(n, lv.n_levels * lv.n_features, device=xyzs.device, dtype=torch.float32) if need_denc else None
+    d_x = torch.empty(n, 3, device=xyzs.device, dtype=torch.float32) if need_x else None
+    check(getattr(_lib(), entry)(_ptr(xyzs), _ptr(table), _ptr(denc), _ptr(ddx), ctypes.byref(lv), n, _ptr(d_denc), _ptr(d_x), _stream()),
+          entry)
+    return d_denc, d_x
+
+
+def hash_bwd2_gather_f32(xyzs, table, denc, ddx, lv, need_denc=True, need_x=True):
+    """Double backward of hash_bwd_input_f32 for ddx [n,3] = d(loss)/d(dx): (d_denc [n, L*F] | None, d_x [n,3] | None), the gradients
+    with respect to denc and to xyzs.  Written, not accumulated; bit-reproducible; an output that is not needed is not computed."""
+    return _hash_bwd2_gather("ngp_hash_bwd2_gather_f32", xyzs, table, torch.float32, denc, ddx, lv, need_denc, need_x)
+
+
+def hash_bwd2_gather_bf16(xyzs, table_bf16, denc, ddx, lv, need_denc=True, need_x=True):
+    """hash_bwd2_gather_f32 for hash_bwd_input_bf16: table_bf16 is the bf16 storage copy the forward gathered from (F = 2)."""
+    return _hash_bwd2_gather("ngp_hash_bwd2_gather_bf16", xyzs, table_bf16, torch.bfloat16, denc, ddx, lv, need_denc, need_x)
+
+
+def hash_bwd2_table_f32(xyzs, denc, ddx, lv, dtable):
+    """dtable += the gradient of hash_bwd_input_{f32,bf16}'s dx with respect to the table, for ddx [n,3] = d(loss)/d(dx): the
+    scatter-add with scale_l * A_c in place of the trilinear weight.  Float atomics: the summation order is not deterministic."""
+    _dev(dtable, torch.float32, "dtable")
+    n = _hash_bwd2_check(xyzs, denc, ddx, lv)
+    if dtable.numel() != lv.total_entries * lv.n_features:
+        raise ValueError("dtable has %d elements, the level table describes %d" % (dtable.numel(), lv.total_entries * lv.n_features))
+    check(_lib().ngp_hash_bwd2_table_f32(_ptr(xyzs), _ptr(denc), _ptr(ddx), ctypes.byref(lv), n, _ptr(dtable), _stream()),
+          "ngp_hash_bwd2_table_f32")
+    _touched(dtable)
+    return dtable
+
+
 # ---------------------------------------------------------------------------------------------------- a-4t
 def make_triplane_levels(base_res, max_res, levels, features):
     """ngp_triplane_levels table (host struct) -- TriPlaneEncoder.__init__ arithmetic (triplane.py:103-160)."""
