@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from composite_reference import distortion_grad64, distortion_loss64
 from test_golden import G, beq, golden_table
 from ngp_hip import ops, synthetic
 
@@ -141,9 +142,7 @@ def test_distortion_golden_and_oracle(hip_lib, oracle):
     # the formula cancels two large prefix products: judge both f32 evaluations against float64
     f64 = np.zeros(2000)
     for r, s0, c in rays_a:
-        wv, tv = ws[s0:s0 + c].astype(np.float64), ts[s0:s0 + c].astype(np.float64)
-        wi, wti = np.cumsum(wv), np.cumsum(wv * tv)
-        f64[r] = np.sum(2 * (wti * (wi - wv) - wi * (wti - wv * tv)) + wv * wv * deltas[s0:s0 + c] / 3)
+        f64[r] = distortion_loss64(ws[s0:s0 + c], ts[s0:s0 + c], deltas[s0:s0 + c])
     err_hip = np.abs(out.detach().cpu().numpy() - f64).max()
     err_ora = np.abs(ref_loss - f64).max()
     assert err_hip <= 3 * err_ora + 1e-6, (err_hip, err_ora)
@@ -154,10 +153,7 @@ def test_distortion_golden_and_oracle(hip_lib, oracle):
     for r, s0, c in rays_a:
         if c == 0:
             continue
-        wv, tv, dv = ws[s0:s0 + c].astype(np.float64), ts[s0:s0 + c].astype(np.float64), deltas[s0:s0 + c].astype(np.float64)
-        wi, wti = np.cumsum(wv), np.cumsum(wv * tv)
-        sel = np.concatenate([[0.0], tv[1:] * wi[:-1] - wti[:-1]])
-        d64[s0:s0 + c] = gl[r] * 2 * (sel + (wti[-1] - wti - tv * (wi[-1] - wi))) + gl[r] * (2.0 / 3.0) * wv * dv
+        d64[s0:s0 + c] = distortion_grad64(gl[r], ws[s0:s0 + c], ts[s0:s0 + c], deltas[s0:s0 + c])
     err_hip = np.abs(w.grad.cpu().numpy() - d64).max()
     err_ora = np.abs(ref_dws - d64).max()
     assert err_hip <= 3 * err_ora + 1e-6 * np.abs(d64).max(), (err_hip, err_ora)
