@@ -22,6 +22,7 @@
 // (bf16 / f16 table: 4-byte gathers, 664 / 600 B).
 #include "ngp_device.h"
 #include "hash_common.h"
+#include "hash_lanes.h"
 #include <hip/hip_fp16.h>
 
 namespace ngp {
@@ -47,18 +48,17 @@ __global__ void __launch_bounds__(256) hash_bwd_input_kernel(const float* __rest
         float d[3] = {0.0f, 0.0f, 0.0f};
         if (gid < total && level < nl) {
             const float x[3] = {xyzs[3 * (size_t)i], xyzs[3 * (size_t)i + 1], xyzs[3 * (size_t)i + 2]};
-            const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level], off = L.offset[level];
-            const float scale = L.scale[level];
-            const bool dense = level < lv.begin_fast_hash_level;
+            const LevelView l = level_at(L, lv, level);
             uint32_t cell[3];
             float fr[3];
-            cell_frac<KIND == TABLE_F16>(x, scale, cell, fr);
+            cell_frac<KIND == TABLE_F16>(x, l.scale, cell, fr);
             float g[F];
             const size_t row = ((size_t)i * nl + level) * F;
             if constexpr (KIND == TABLE_F16) {
                 const float2 gh = __half22float2(*reinterpret_cast<const __half2*>(reinterpret_cast<const __half*>(denc_v) + row));
                 g[0] = gh.x; g[1] = gh.y;
             } else {
+                // = load_row<F>(gp, g), spelled out: through the call F = 8 goes from 92 to 106 VGPRs and loses a wave per SIMD
                 const float* gp = reinterpret_cast<const float*>(denc_v) + row;
                 if constexpr (F == 2) { const float2 t = *reinterpret_cast<const float2*>(gp); g[0] = t.x; g[1] = t.y; }
                 else if constexpr (F == 4) { const float4 t = *reinterpret_cast<const float4*>(gp); g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w; }
@@ -70,21 +70,16 @@ __global__ void __launch_bounds__(256) hash_bwd_input_kernel(const float* __rest
             float v[8][F];
 #pragma unroll
             for (int ci = 0; ci < 8; ++ci) {
-                const size_t e = (size_t)off + level_index(dense, mode, size, res, cell[0] + (ci & 1), cell[1] + ((ci >> 1) & 1), cell[2] + (ci >> 2));
+                const size_t e = (size_t)l.offset + level_index(l.dense, l.mode, l.size, l.res, cell[0] + (ci & 1), cell[1] + ((ci >> 1) & 1), cell[2] + (ci >> 2));
                 if constexpr (KIND == TABLE_BF16) {
-                    const uint32_t u = reinterpret_cast<const uint32_t*>(table_v)[e];
-                    v[ci][0] = __uint_as_float(u << 16); v[ci][1] = __uint_as_float(u & 0xffff0000u);
+                    const float2 t = bf16x2_to_f32(reinterpret_cast<const uint32_t*>(table_v)[e]);
+                    v[ci][0] = t.x; v[ci][1] = t.y;
                 } else if constexpr (KIND == TABLE_F16) {
                     const float2 t = __half22float2(reinterpret_cast<const __half2*>(table_v)[e]);
                     v[ci][0] = t.x; v[ci][1] = t.y;
                 } else {
                     const float* p = reinterpret_cast<const float*>(table_v) + e * F;
-                    if constexpr (F == 2) { const float2 t = *reinterpret_cast<const float2*>(p); v[ci][0] = t.x; v[ci][1] = t.y; }
-                    else if constexpr (F == 4) { const float4 t = *reinterpret_cast<const float4*>(p); v[ci][0] = t.x; v[ci][1] = t.y; v[ci][2] = t.z; v[ci][3] = t.w; }
-                    else {
-#pragma unroll
-                        for (int f = 0; f < F; ++f) v[ci][f] = p[f];
-                    }
+                    load_row<F>(p, v[ci]);
                 }
             }
             float t[8];                                        // t_c = sum_f denc_f * T_c,f
@@ -107,14 +102,10 @@ __global__ void __launch_bounds__(256) hash_bwd_input_kernel(const float* __rest
                         const int near = (a << j) | (b << m);  // corner with bit k clear
                         s += (w[j][a] * w[m][b]) * (t[near | (1 << k)] - t[near]);
                     }
-                d[k] = scale * s;
+                d[k] = l.scale * s;
             }
         }
-        // fixed-order tree over the group's lanes (group is a power of two <= 16 and divides the wave: partners stay in the group)
-        for (int step = group >> 1; step >= 1; step >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) d[k] += __shfl_xor(d[k], step, NGP_WAVE);
-        }
+        group_tree_sum3(d, group);
         if (gid < total && level == 0) {
             float* o = dxyzs + 3 * (size_t)i;
             o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
@@ -124,13 +115,9 @@ __global__ void __launch_bounds__(256) hash_bwd_input_kernel(const float* __rest
 
 template <int F, int KIND>
 static int launch_bwd_input(const float* xyzs, const void* table, const void* denc, const ngp_hash_levels* lv, int n, float* dxyzs, void* stream) {
-    int group = 1;
-    while (group < lv->n_levels) group <<= 1;
-    const long long lanes = (long long)n * group;
-    long long blocks = (lanes + 255) / 256;
-    if (blocks > 256LL * 16) blocks = 256LL * 16;            // 256 CUs x 16 blocks, block-stride beyond that
-    hipLaunchKernelGGL((hash_bwd_input_kernel<F, KIND>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyzs, table, denc, *lv, n,
-                       group, dxyzs);
+    const SampleLevelGrid g = sample_level_grid(lv, n);
+    hipLaunchKernelGGL((hash_bwd_input_kernel<F, KIND>), dim3(g.blocks), dim3(256), 0, (hipStream_t)stream, xyzs, table, denc, *lv, n,
+                       g.group, dxyzs);
     NGP_LAUNCH_CHECK();
     return 0;
 }

@@ -25,17 +25,18 @@
 // F = 2, L = 16: 16 x (64 B gathered + 8 B denc + 8 B d_denc) + 12 B position + 12 B ddx + 12 B d_x = 1316 B per sample.
 //
 // Scatter (hash_bwd2_table_f32x2_kernel, F = 2; hash_bwd2_table_kernel<F> otherwise): the first-order scatter-add of hash_grid.hip with
-// scale_l * A_c in place of the trilinear weight -- lane quads on one 64-byte line, a wave of 16 consecutive samples per level, a
-// segmented scan over equal-cell runs, only the run's tail issuing unsafeAtomicAdd; contributions that are exactly 0 are skipped.
-// It does not read the table, so one kernel serves the fp32 and the bf16-copy encoder (the gradient goes to the fp32 master).
-// These are float atomics: the summation order, and with it the last bits of d_table, is NOT deterministic from run to run, as in
-// the first-order scatter.
+// scale_l * A_c in place of the trilinear weight -- for F = 2 the same body, scatter_runs_f32x2 (hash_lanes.h).  It does not read the
+// table, so one kernel serves the fp32 and the bf16-copy encoder (the gradient goes to the fp32 master).  Float atomics: the summation
+// order, and with it the last bits of d_table, is NOT deterministic from run to run, as in the first-order scatter.
 #include "ngp_device.h"
 #include "hash_common.h"
+#include "hash_lanes.h"
 
 namespace ngp {
 
 // BF16: the table is the bf16 storage copy (pairs, F = 2), widened exactly; everything else is the f32 kind.
+// The lane mapping, corner gather and difference loop are hash_bwd_input_kernel's, spelled out in both: through shared helpers they
+// compile to other schedules, this kernel to a slower one (profiles/hash_lanes_refactor.md).  The rest comes from hash_lanes.h.
 template <int F, bool BF16>
 __global__ void __launch_bounds__(256) hash_bwd2_gather_kernel(const float* __restrict__ xyzs, const void* __restrict__ table_v,
                                                                const float* __restrict__ denc, const float* __restrict__ ddx,
@@ -55,38 +56,23 @@ __global__ void __launch_bounds__(256) hash_bwd2_gather_kernel(const float* __re
         if (gid < total && level < nl) {
             const float x[3] = {xyzs[3 * (size_t)i], xyzs[3 * (size_t)i + 1], xyzs[3 * (size_t)i + 2]};
             const float u[3] = {ddx[3 * (size_t)i], ddx[3 * (size_t)i + 1], ddx[3 * (size_t)i + 2]};
-            const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level], off = L.offset[level];
-            const float scale = L.scale[level];
-            const bool dense = level < lv.begin_fast_hash_level;
+            const LevelView l = level_at(L, lv, level);
             uint32_t cell[3];
             float fr[3];
-            cell_frac<false>(x, scale, cell, fr);
+            cell_frac<false>(x, l.scale, cell, fr);
             float g[F];
             const size_t row = ((size_t)i * nl + level) * F;
-            {
-                const float* gp = denc + row;
-                if constexpr (F == 2) { const float2 t = *reinterpret_cast<const float2*>(gp); g[0] = t.x; g[1] = t.y; }
-                else if constexpr (F == 4) { const float4 t = *reinterpret_cast<const float4*>(gp); g[0] = t.x; g[1] = t.y; g[2] = t.z; g[3] = t.w; }
-                else {
-#pragma unroll
-                    for (int f = 0; f < F; ++f) g[f] = gp[f];
-                }
-            }
+            load_row<F>(denc + row, g);
             float v[8][F];
 #pragma unroll
             for (int ci = 0; ci < 8; ++ci) {
-                const size_t e = (size_t)off + level_index(dense, mode, size, res, cell[0] + (ci & 1), cell[1] + ((ci >> 1) & 1), cell[2] + (ci >> 2));
+                const size_t e = (size_t)l.offset + level_index(l.dense, l.mode, l.size, l.res, cell[0] + (ci & 1), cell[1] + ((ci >> 1) & 1), cell[2] + (ci >> 2));
                 if constexpr (BF16) {
-                    const uint32_t p = reinterpret_cast<const uint32_t*>(table_v)[e];
-                    v[ci][0] = __uint_as_float(p << 16); v[ci][1] = __uint_as_float(p & 0xffff0000u);
+                    const float2 t = bf16x2_to_f32(reinterpret_cast<const uint32_t*>(table_v)[e]);
+                    v[ci][0] = t.x; v[ci][1] = t.y;
                 } else {
                     const float* p = reinterpret_cast<const float*>(table_v) + e * F;
-                    if constexpr (F == 2) { const float2 t = *reinterpret_cast<const float2*>(p); v[ci][0] = t.x; v[ci][1] = t.y; }
-                    else if constexpr (F == 4) { const float4 t = *reinterpret_cast<const float4*>(p); v[ci][0] = t.x; v[ci][1] = t.y; v[ci][2] = t.z; v[ci][3] = t.w; }
-                    else {
-#pragma unroll
-                        for (int f = 0; f < F; ++f) v[ci][f] = p[f];
-                    }
+                    load_row<F>(p, v[ci]);
                 }
             }
             const float w[3][2] = {{1.0f - fr[0], fr[0]}, {1.0f - fr[1], fr[1]}, {1.0f - fr[2], fr[2]}};
@@ -108,15 +94,10 @@ __global__ void __launch_bounds__(256) hash_bwd2_gather_kernel(const float* __re
                             }
                         acc += u[k] * s;
                     }
-                    o[f] = scale * acc;
+                    o[f] = l.scale * acc;
                 }
                 float* op = d_denc + row;
-                if constexpr (F == 2) *reinterpret_cast<float2*>(op) = make_float2(o[0], o[1]);
-                else if constexpr (F == 4) *reinterpret_cast<float4*>(op) = make_float4(o[0], o[1], o[2], o[3]);
-                else {
-#pragma unroll
-                    for (int f = 0; f < F; ++f) op[f] = o[f];
-                }
+                store_row<F>(op, o);
             }
             if (d_xyzs) {
                 float t[8];                                        // t_c = sum_f denc_f * T_c,f
@@ -139,32 +120,20 @@ __global__ void __launch_bounds__(256) hash_bwd2_gather_kernel(const float* __re
                     }
                     M[j] = s;
                 }
-                const float s2 = scale * scale;
+                const float s2 = l.scale * l.scale;
                 d[0] = s2 * (u[1] * M[2] + u[2] * M[1]);           // M_xy = M[2], M_yz = M[0], M_zx = M[1]
                 d[1] = s2 * (u[0] * M[2] + u[2] * M[0]);
                 d[2] = s2 * (u[0] * M[1] + u[1] * M[0]);
             }
         }
         if (d_xyzs) {                                              // uniform over the grid: every lane of the wave takes the shuffles
-            // fixed-order tree over the group's lanes (group is a power of two <= 16 and divides the wave: partners stay in the group)
-            for (int step = group >> 1; step >= 1; step >>= 1) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) d[k] += __shfl_xor(d[k], step, NGP_WAVE);
-            }
+            group_tree_sum3(d, group);
             if (gid < total && level == 0) {
                 float* o = d_xyzs + 3 * (size_t)i;
                 o[0] = d[0]; o[1] = d[1]; o[2] = d[2];
             }
         }
     }
-}
-
-// A_c of corner (xb, yb, zb) for w[axis][bit] and u = ddx: sum_k u_k * s_k(c) * prod_{j != k} w_j(c_j).
-__device__ __forceinline__ float corner_A(const float w[3][2], const float u[3], int xb, int yb, int zb) {
-    const float ax = (xb ? u[0] : -u[0]) * (w[1][yb] * w[2][zb]);
-    const float ay = (yb ? u[1] : -u[1]) * (w[2][zb] * w[0][xb]);
-    const float az = (zb ? u[2] : -u[2]) * (w[0][xb] * w[1][yb]);
-    return (ax + ay) + az;
 }
 
 // Generic F: one lane per (sample, level), F*8 independent atomics (the shape of hash_bwd_f32_kernel).
@@ -186,18 +155,16 @@ __global__ void __launch_bounds__(256) hash_bwd2_table_kernel(const float* __res
         const float u[3] = {ddx[3 * (size_t)i], ddx[3 * (size_t)i + 1], ddx[3 * (size_t)i + 2]};
         if (!any || (u[0] == 0.0f && u[1] == 0.0f && u[2] == 0.0f)) continue;       // exact-zero rows contribute nothing
         const float x[3] = {xyzs[3 * (size_t)i], xyzs[3 * (size_t)i + 1], xyzs[3 * (size_t)i + 2]};
-        const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level], off = L.offset[level];
-        const float scale = L.scale[level];
-        const bool dense = level < lv.begin_fast_hash_level;
+        const LevelView l = level_at(L, lv, level);
         uint32_t cell[3];
         float fr[3];
-        cell_frac<false>(x, scale, cell, fr);
+        cell_frac<false>(x, l.scale, cell, fr);
         const float w[3][2] = {{1.0f - fr[0], fr[0]}, {1.0f - fr[1], fr[1]}, {1.0f - fr[2], fr[2]}};
 #pragma unroll
         for (int ci = 0; ci < 8; ++ci) {
             const int xb = ci & 1, yb = (ci >> 1) & 1, zb = ci >> 2;
-            const size_t e = (size_t)off + level_index(dense, mode, size, res, cell[0] + xb, cell[1] + yb, cell[2] + zb);
-            const float a = scale * corner_A(w, u, xb, yb, zb);
+            const size_t e = (size_t)l.offset + level_index(l.dense, l.mode, l.size, l.res, cell[0] + xb, cell[1] + yb, cell[2] + zb);
+            const float a = l.scale * corner_A(w, u, xb, yb, zb);
 #pragma unroll
             for (int f = 0; f < F; ++f) {
                 const float c = a * g[f];
@@ -207,84 +174,39 @@ __global__ void __launch_bounds__(256) hash_bwd2_table_kernel(const float* __res
     }
 }
 
-// F = 2: the shape of hash_bwd_f32x2_kernel (hash_grid.hip).  Lane quad = (sample, x-corner bit, feature): the quad's four atomics
-// land on one 64-byte line 7 times out of 8; one wave = 16 consecutive samples x one level; equal-cell runs are summed with a
-// segmented wave scan and only the last lane of a run issues atomics.
-__global__ void __launch_bounds__(256) hash_bwd2_table_f32x2_kernel(const float* __restrict__ xyzs, const float* __restrict__ denc,
-                                                                    const float* __restrict__ ddx, ngp_hash_levels lv, int n,
-                                                                    float* __restrict__ dtable) {
-    __shared__ LevelLDS L;
-    load_levels(lv, L);
-    const int nl = lv.n_levels, bfhl = lv.begin_fast_hash_level;
-    const int lane = threadIdx.x & 63;
-    const int s_in = lane >> 2, xb = (lane >> 1) & 1, f = lane & 1;
-    const int n_tiles = (n + 15) >> 4;
-    const int waves_per_block = blockDim.x >> 6;
-    for (int tile = blockIdx.x * waves_per_block + (threadIdx.x >> 6); tile < n_tiles; tile += gridDim.x * waves_per_block) {
-        const int i = tile * 16 + s_in;
-        const bool valid = i < n;
-        float p[3] = {0.f, 0.f, 0.f}, u[3] = {0.f, 0.f, 0.f};
+// F = 2: scatter_runs_f32x2 (hash_lanes.h), the body of hash_bwd_f32x2_kernel, with scale_l * A_c in place of the trilinear weight.
+struct SecondOrderRows {
+    const float *__restrict__ xyzs, *__restrict__ denc, *__restrict__ ddx;
+    int nl;
+    float u[3];
+    __device__ __forceinline__ int count(int n) const { return n; }
+    __device__ __forceinline__ void fetch(int i, bool valid, float (&p)[3]) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) p[k] = u[k] = 0.f;
         if (valid) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) { p[k] = xyzs[3 * (size_t)i + k]; u[k] = ddx[3 * (size_t)i + k]; }
         }
-        for (int level = 0; level < nl; ++level) {
-            const float g = valid ? denc[(size_t)i * (size_t)(nl * 2) + level * 2 + f] : 0.0f;
-            const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level];
-            const float scale = L.scale[level];
-            uint32_t cell[3];
-            float fr[3];
-            cell_frac<false>(p, scale, cell, fr);
-            const uint32_t cx = cell[0], cy = cell[1], cz = cell[2];
-            // run structure: head = first sample of the tile or a different cell than the previous sample
-            const uint32_t pcx = __shfl_up(cx, 4, 64), pcy = __shfl_up(cy, 4, 64), pcz = __shfl_up(cz, 4, 64);
-            const int pvalid = __shfl_up((int)valid, 4, 64);
-            const bool head = (s_in == 0) || !valid || !pvalid || cx != pcx || cy != pcy || cz != pcz;
-            const int nhead = __shfl_down((int)head, 4, 64);
-            const bool tail = valid && ((s_in == 15) || nhead);
-            const float w[3][2] = {{1.0f - fr[0], fr[0]}, {1.0f - fr[1], fr[1]}, {1.0f - fr[2], fr[2]}};
-            float v[4];
-            uint32_t e[4];
-            const bool dense = level < bfhl;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {              // k = (z bit, y bit)
-                e[k] = L.offset[level] + level_index(dense, mode, size, res, cx + (uint32_t)xb, cy + (uint32_t)(k & 1), cz + (uint32_t)(k >> 1));
-                v[k] = (scale * corner_A(w, u, xb, k & 1, k >> 1)) * g;
-            }
-            // segmented inclusive scan over samples (lane distance 4 = one sample)
-            bool hf = head;
-#pragma unroll
-            for (int d = 4; d < 64; d <<= 1) {
-                const int hup = __shfl_up((int)hf, d, 64);
-                float vup[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) vup[k] = __shfl_up(v[k], d, 64);
-                if (lane >= d && !hf) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] += vup[k];
-                    hf = hup != 0;
-                }
-            }
-            if (tail) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (v[k] != 0.0f) unsafeAtomicAdd(dtable + (size_t)e[k] * 2 + f, v[k]);
-            }
-        }
     }
+    __device__ __forceinline__ float grad(int i, int level, int f) const { return denc[(size_t)i * (size_t)(nl * 2) + level * 2 + f]; }
+    __device__ __forceinline__ void seen(float) const {}
+    __device__ __forceinline__ float weight(const float fr[3], float scale, int xb, int yb, int zb) const {
+        const float w[3][2] = {{1.0f - fr[0], fr[0]}, {1.0f - fr[1], fr[1]}, {1.0f - fr[2], fr[2]}};
+        return scale * corner_A(w, u, xb, yb, zb);
+    }
+};
+__global__ void __launch_bounds__(256) hash_bwd2_table_f32x2_kernel(const float* __restrict__ xyzs, const float* __restrict__ denc,
+                                                                    const float* __restrict__ ddx, ngp_hash_levels lv, int n, float* __restrict__ dtable) {
+    scatter_runs_f32x2(lv, n, dtable, blockDim.x, SecondOrderRows{xyzs, denc, ddx, lv.n_levels, {}});
 }
 
 template <int F, bool BF16>
 static int launch_bwd2_gather(const float* xyzs, const void* table, const float* denc, const float* ddx, const ngp_hash_levels* lv, int n,
                               float* d_denc, float* d_xyzs, void* stream) {
     if (!d_denc && !d_xyzs) return 0;
-    int group = 1;
-    while (group < lv->n_levels) group <<= 1;
-    const long long lanes = (long long)n * group;
-    long long blocks = (lanes + 255) / 256;
-    if (blocks > 256LL * 16) blocks = 256LL * 16;            // 256 CUs x 16 blocks, block-stride beyond that
-    hipLaunchKernelGGL((hash_bwd2_gather_kernel<F, BF16>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyzs, table, denc, ddx,
-                       *lv, n, group, d_denc, d_xyzs);
+    const SampleLevelGrid g = sample_level_grid(lv, n);
+    hipLaunchKernelGGL((hash_bwd2_gather_kernel<F, BF16>), dim3(g.blocks), dim3(256), 0, (hipStream_t)stream, xyzs, table, denc, ddx,
+                       *lv, n, g.group, d_denc, d_xyzs);
     NGP_LAUNCH_CHECK();
     return 0;
 }

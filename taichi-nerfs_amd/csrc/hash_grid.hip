@@ -16,6 +16,7 @@
 // The backward kernels optionally run over a compacted list of live samples (live_idx).  The level table sits in LDS.
 #include "ngp_device.h"
 #include "hash_common.h"
+#include "hash_lanes.h"
 #include <hip/hip_fp16.h>
 
 namespace ngp {
@@ -91,10 +92,6 @@ __device__ __forceinline__ bool corners_flat(const LevelRegs& lr, float x, float
 
 // BF16 = true: the table is stored as bf16 pairs (uint32 per entry, F = 2 only); bf16 -> f32 is exact, the interpolation and
 // the output stay f32, so the result equals the f32 kernel run on the bf16-rounded table, bit for bit.
-__device__ __forceinline__ float2 bf16x2_to_f32(uint32_t u) {
-    return make_float2(__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u));
-}
-
 template <int F, bool BF16 = false>
 __global__ void __launch_bounds__(256) hash_fwd_f32_kernel(const float* __restrict__ xyzs, const float* __restrict__ table,
                                                            ngp_hash_levels lv, int n, const int32_t* __restrict__ n_dev,
@@ -116,12 +113,7 @@ __global__ void __launch_bounds__(256) hash_fwd_f32_kernel(const float* __restri
         for (int ci = 0; ci < 8; ++ci) {
             const float* p = table + (size_t)c.idx[ci] * F;
             if constexpr (BF16) { float2 t = bf16x2_to_f32(reinterpret_cast<const uint32_t*>(table)[c.idx[ci]]); v[ci][0] = t.x; v[ci][1] = t.y; }
-            else if constexpr (F == 2) { float2 t = *reinterpret_cast<const float2*>(p); v[ci][0] = t.x; v[ci][1] = t.y; }
-            else if constexpr (F == 4) { float4 t = *reinterpret_cast<const float4*>(p); v[ci][0] = t.x; v[ci][1] = t.y; v[ci][2] = t.z; v[ci][3] = t.w; }
-            else {
-#pragma unroll
-                for (int f = 0; f < F; ++f) v[ci][f] = p[f];
-            }
+            else load_row<F>(p, v[ci]);
         }
         float acc[F];
 #pragma unroll
@@ -130,13 +122,7 @@ __global__ void __launch_bounds__(256) hash_fwd_f32_kernel(const float* __restri
         for (int ci = 0; ci < 8; ++ci)
 #pragma unroll
             for (int f = 0; f < F; ++f) acc[f] += c.w[ci] * v[ci][f];               // :139-140 (mul then add)
-        float* o = out + (size_t)gid * F;
-        if constexpr (F == 2) *reinterpret_cast<float2*>(o) = make_float2(acc[0], acc[1]);
-        else if constexpr (F == 4) *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        else {
-#pragma unroll
-            for (int f = 0; f < F; ++f) o[f] = acc[f];
-        }
+        store_row<F>(out + (size_t)gid * F, acc);
     }
 }
 
@@ -314,82 +300,32 @@ __global__ void __launch_bounds__(256) hash_bwd_f32_kernel(const float* __restri
     }
 }
 
-// F = 2 fast path, shaped by what the MI355X atomic pipeline charges for (profiles/microbench/atomics2.hip):
-// a float atomic instruction costs one request per DISTINCT 64-byte line it touches (~21 G lines/s chip-wide),
-// adjacent lanes on one line are free, and duplicate addresses inside an instruction are NOT merged.
-//   * lane quad = (sample, x-corner bit, feature): the four lanes of a quad hit (e, f0) (e, f1) (e', f0) (e', f1)
-//     where e' is the x-neighbour entry -- adjacent (dense levels) or e^small-mask (xor hash) -- so the quad lands
-//     on one 64-B line 7 times out of 8: ~4 line requests per (sample, level) instead of 16 scattered atomics.
-//   * one wave = 16 consecutive samples x one level; consecutive samples of a ray sit in the same cell on the
-//     coarse/mid levels, so equal-cell runs are summed with a segmented wave scan and only the last lane of a
-//     run issues atomics (removes the in-instruction duplicates and ~60 % of all requests).
-// Summation order differs from a serial loop: tolerance-checked against the oracle (float atomics are
-// order-nondeterministic in the reference too).
-__global__ void __launch_bounds__(256) hash_bwd_f32x2_kernel(const float* __restrict__ xyzs, const float* __restrict__ dout,
-                                                             ngp_hash_levels lv, int n, const int32_t* __restrict__ n_dev,
-                                                             const int32_t* __restrict__ idx, XyzNorm nm, int enc_pairs,
-                                                             float* __restrict__ dtable, int32_t* __restrict__ found_inf) {
-    __shared__ LevelLDS L;
-    load_levels(lv, L);
-    const size_t plane = (size_t)n;
-    if (n_dev) n = min(n, *n_dev);
-    const int nl = lv.n_levels, bfhl = lv.begin_fast_hash_level;
-    const int lane = threadIdx.x & 63;
-    const int s_in = lane >> 2, xb = (lane >> 1) & 1, f = lane & 1;
-    const int n_tiles = (n + 15) >> 4;
-    const int waves_per_block = blockDim.x >> 6;
-    for (int tile = blockIdx.x * waves_per_block + (threadIdx.x >> 6); tile < n_tiles; tile += gridDim.x * waves_per_block) {
-        const int i = tile * 16 + s_in;                  // position in dout (and in the live list, when there is one)
-        const bool valid = i < n;
-        float x = 0.f, y = 0.f, z = 0.f;
+// F = 2 fast path: scatter_runs_f32x2 (hash_lanes.h) over the trilinear weight and the trainer's gradient rows -- an optional list of
+// live samples (idx), natural or pair-major dout, a device-side count, the fused position normalisation, GradScaler's inf/nan check.
+// Summation order differs from a serial loop: tolerance-checked against the oracle (the reference's float atomics are unordered too).
+struct FirstOrderRows {
+    const float *__restrict__ xyzs, *__restrict__ dout;
+    const int32_t *__restrict__ n_dev, *__restrict__ idx;
+    XyzNorm nm;
+    int enc_pairs, nl;
+    size_t plane;                        // the pair-major layout's plane stride: n before the device-side count
+    int32_t* __restrict__ found_inf;
+    __device__ __forceinline__ int count(int n) const { return n_dev ? min(n, *n_dev) : n; }
+    __device__ __forceinline__ void fetch(int i, bool valid, float (&p)[3]) const {
+        p[0] = p[1] = p[2] = 0.f;
         if (valid) {
             const size_t src = idx ? (size_t)idx[i] : (size_t)i;
-            x = norm01(nm, xyzs[3 * src]); y = norm01(nm, xyzs[3 * src + 1]); z = norm01(nm, xyzs[3 * src + 2]);
-        }
-        for (int level = 0; level < nl; ++level) {
-            const float g = valid ? enc_ptr(dout, level, (size_t)i, plane, enc_pairs, nl)[f] : 0.0f;
-            if (found_inf && !isfinite(g)) *found_inf = 1;          // GradScaler's inf/nan check, done where the data passes
-            const uint32_t res = L.res[level], size = L.size[level], mode = L.mode[level];
-            const float p[3] = {x, y, z};
-            uint32_t cell[3];
-            float fr[3];
-            cell_frac<false>(p, L.scale[level], cell, fr);
-            const uint32_t cx = cell[0], cy = cell[1], cz = cell[2];
-            // run structure: head = first sample of the tile or a different cell than the previous sample
-            const uint32_t pcx = __shfl_up(cx, 4, 64), pcy = __shfl_up(cy, 4, 64), pcz = __shfl_up(cz, 4, 64);
-            const int pvalid = __shfl_up((int)valid, 4, 64);
-            bool head = (s_in == 0) || !valid || !pvalid || cx != pcx || cy != pcy || cz != pcz;
-            const int nhead = __shfl_down((int)head, 4, 64);
-            const bool tail = valid && ((s_in == 15) || nhead);
-            float v[4];
-            uint32_t e[4];
-            const bool dense = level < bfhl;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {              // k = (z bit, y bit)
-                e[k] = L.offset[level] + level_index(dense, mode, size, res, cx + (uint32_t)xb, cy + (uint32_t)(k & 1), cz + (uint32_t)(k >> 1));
-                v[k] = corner_weight(2 * k + xb, fr) * g;
-            }
-            // segmented inclusive scan over samples (lane distance 4 = one sample)
-            bool hf = head;
-#pragma unroll
-            for (int d = 4; d < 64; d <<= 1) {
-                const int hup = __shfl_up((int)hf, d, 64);
-                float vup[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) vup[k] = __shfl_up(v[k], d, 64);
-                if (lane >= d && !hf) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] += vup[k];
-                    hf = hup != 0;
-                }
-            }
-            if (tail) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (v[k] != 0.0f) unsafeAtomicAdd(dtable + (size_t)e[k] * 2 + f, v[k]);
-            }
+            p[0] = norm01(nm, xyzs[3 * src]); p[1] = norm01(nm, xyzs[3 * src + 1]); p[2] = norm01(nm, xyzs[3 * src + 2]);
         }
     }
+    __device__ __forceinline__ float grad(int i, int level, int f) const { return enc_ptr(dout, level, (size_t)i, plane, enc_pairs, nl)[f]; }
+    __device__ __forceinline__ void seen(float g) const { if (found_inf && !isfinite(g)) *found_inf = 1; }   // where the data passes
+    __device__ __forceinline__ float weight(const float fr[3], float, int xb, int yb, int zb) const { return corner_weight(xb | (yb << 1) | (zb << 2), fr); }
+};
+__global__ void __launch_bounds__(256) hash_bwd_f32x2_kernel(const float* __restrict__ xyzs, const float* __restrict__ dout, ngp_hash_levels lv,
+                                                             int n, const int32_t* __restrict__ n_dev, const int32_t* __restrict__ idx, XyzNorm nm,
+                                                             int enc_pairs, float* __restrict__ dtable, int32_t* __restrict__ found_inf) {
+    scatter_runs_f32x2(lv, n, dtable, blockDim.x, FirstOrderRows{xyzs, dout, n_dev, idx, nm, enc_pairs, lv.n_levels, (size_t)n, found_inf});
 }
 
 // ---- half2 forward (hash_encoder_half.py:112-161): f16 table, f16 accumulate ---------------------------
@@ -484,22 +420,20 @@ __global__ void __launch_bounds__(256) hash_bwd_f16x2_kernel(const float* __rest
             uint32_t cell[3];
             float fr[3];
             cell_frac<true>(p, L.scale[level], cell, fr);
-            const uint32_t cx = cell[0], cy = cell[1], cz = cell[2];
-            const uint32_t pcx = __shfl_up(cx, 2, 64), pcy = __shfl_up(cy, 2, 64), pcz = __shfl_up(cz, 2, 64);
-            const int pvalid = __shfl_up((int)valid, 2, 64);
-            const bool head = (s_in == 0) || !valid || !pvalid || cx != pcx || cy != pcy || cz != pcz;
-            const int nhead = __shfl_down((int)head, 2, 64);
-            const bool tail = valid && ((s_in == 31) || nhead);
+            bool head, tail;
+            run_head_tail<2>(cell, valid, s_in, 31, head, tail);
             float v0[4], v1[4];
             uint32_t e[4];
             const bool dense = level < bfhl;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {              // k = (z bit, y bit)
-                e[k] = L.offset[level] + level_index(dense, mode, size, res, cx + (uint32_t)xb, cy + (uint32_t)(k & 1), cz + (uint32_t)(k >> 1));
+                e[k] = L.offset[level] + level_index(dense, mode, size, res, cell[0] + (uint32_t)xb, cell[1] + (uint32_t)(k & 1), cell[2] + (uint32_t)(k >> 1));
                 const float w = corner_weight(2 * k + xb, fr);
                 const float2 r = make_float2(f16_round(w * g.x), f16_round(w * g.y));          // cast(w * g, f16) :205-208 (f32 product first)
                 v0[k] = r.x; v1[k] = r.y;
             }
+            // = seg_scan_up<2> (hash_lanes.h) over v0 and v1 together; spelled out: through the helper on one 8-wide array the
+            // kernel's instruction list changes, and nothing in the tree times this kernel
             bool hf = head;
 #pragma unroll
             for (int d = 2; d < 64; d <<= 1) {
