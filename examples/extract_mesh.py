@@ -1,0 +1,166 @@
+"""Save a mesh: sample a field on a regular grid and extract its isosurface by marching tetrahedra on the GPU (ngp_hip/mesh.py).
+
+    python examples/extract_mesh.py --sdf --steps 500 --out sphere.ply                   # fit the sphere SDF, extract f = 0
+    python examples/extract_mesh.py --train_steps 1000 --resolution 256 --out scene.ply   # train on the procedural scene, extract
+    python examples/extract_mesh.py --ckpt model.pth --resolution 256 --out scene.obj     # a saved NGP state_dict
+
+--sdf fits f(x) = MLP(HashEncoder(x)) to the signed distance of a sphere (centre 0.5, radius 0.3) in [0, 1]^3 with an eikonal term, as
+examples/fit_sdf_eikonal.py does, and extracts the zero level with sign=-1 (solid where f < 0).  The other two modes extract the surface
+density = threshold of an Instant-NGP model; the default threshold is the occupancy threshold of the training loop,
+0.01 * MAX_SAMPLES / sqrt(3).  The file type follows the suffix of --out (.ply binary little-endian, .obj text).  One JSON line reports
+V, T, the Euler characteristic V - E + T, the number of boundary edges (0 = closed surface) and the times."""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "taichi-nerfs_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+
+def fit_sphere_sdf(args, dev):
+    """The fit of examples/fit_sdf_eikonal.py -> (callable points [n,3] -> f [n], last SDF loss)."""
+    from modules.hash_encoder import HashEncoder
+    torch.manual_seed(args.seed)
+    enc = HashEncoder(max_params=2**args.log2_T, levels=args.levels, max_res=args.max_res, twice_differentiable=True).to(dev)
+    with torch.no_grad():
+        enc.hash_table.uniform_(-1e-4, 1e-4)
+    mlp = torch.nn.Sequential(torch.nn.Linear(enc.out_dim, args.width), torch.nn.Softplus(beta=100.0), torch.nn.Linear(args.width, 1)).to(dev)
+    opt = torch.optim.Adam(list(enc.parameters()) + list(mlp.parameters()), lr=args.lr, eps=1e-15)
+    gen = torch.Generator(dev).manual_seed(args.seed)
+    sdf_loss = torch.zeros((), device=dev)
+    for _ in range(args.steps):
+        x = torch.rand(args.n, 3, device=dev, generator=gen).requires_grad_()
+        f = mlp(enc(x)).squeeze(1)
+        (grad,) = torch.autograd.grad(f.sum(), x, create_graph=True)
+        sdf_loss = (f - (torch.linalg.norm(x.detach() - 0.5, dim=1) - 0.3)).abs().mean()
+        loss = sdf_loss + args.eikonal_weight * ((torch.linalg.norm(grad, dim=1) - 1.0) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+    return (lambda pts: mlp(enc(pts.contiguous())).squeeze(1)), float(sdf_loss.detach())
+
+
+def _cameras(n, radius, seed, device):
+    g = torch.Generator().manual_seed(seed)
+    z = 0.1 + 0.8 * torch.rand(n, generator=g)
+    phi = 2 * math.pi * torch.rand(n, generator=g)
+    r = (1 - z * z).sqrt()
+    pos = radius * torch.stack([r * torch.cos(phi), r * torch.sin(phi), z], -1)
+    fwd = F.normalize(-pos, dim=-1)
+    right = F.normalize(torch.cross(fwd, torch.tensor([0.0, 0.0, 1.0]).expand_as(fwd), dim=-1), dim=-1)
+    down = torch.cross(fwd, right, dim=-1)
+    return torch.cat([torch.stack([right, down, fwd], -1), pos[..., None]], -1).to(device)
+
+
+def train_procedural_model(steps, dev, wh=100, n_views=40, batch=8192):
+    """An NGP trained on the procedural scene of ngp_hip.synthetic with the schedule of examples/train_procedural.py (FusedTrainer,
+    occupancy update every 16 steps, 256 warm-up steps) -> (model, occupancy threshold)."""
+    from modules.networks import NGP
+    from modules.rendering import MAX_SAMPLES
+    from ngp_hip.rays import RayBatcher
+    from ngp_hip.synthetic import procedural_render_gt
+    from ngp_hip.trainer import FusedTrainer
+    torch.manual_seed(23)
+    focal = 1111.1 * wh / 800
+    ys, xs = torch.meshgrid(torch.arange(wh, device=dev), torch.arange(wh, device=dev), indexing="ij")
+    dirs = torch.stack([(xs - wh / 2 + 0.5) / focal, (ys - wh / 2 + 0.5) / focal, torch.ones_like(xs, dtype=torch.float32)], -1).reshape(-1, 3)
+    poses = _cameras(n_views, 1.39, 23, dev)
+    imgs = torch.stack([procedural_render_gt(p[:, 3].expand_as(dirs), dirs @ p[:, :3].T) for p in poses])
+    model = NGP(scale=0.5, max_res=1024).to(dev)
+    K = torch.tensor([[focal, 0, wh / 2], [0, focal, wh / 2], [0, 0, 1]], device=dev)
+    model.mark_invisible_cells(K, poses, (wh, wh))
+    trainer = FusedTrainer(model, lr=1e-2, max_steps=max(steps, 1))
+    batcher = RayBatcher(imgs, poses, dirs, batch_size=batch)
+    thr = 0.01 * MAX_SAMPLES / 3**0.5
+    for step in range(steps):
+        cur = batcher.sample()
+        if step % 16 == 0:
+            trainer.update_density_grid(thr, warmup=step < 256)
+        trainer.step(cur["rays_o"], cur["rays_d"], cur["rgb"])
+    torch.cuda.synchronize()
+    return model, thr
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    mode = ap.add_mutually_exclusive_group(required=True)
+    mode.add_argument("--sdf", action="store_true", help="fit the sphere SDF and extract its zero level")
+    mode.add_argument("--train_steps", type=int, help="train an NGP on the procedural scene for this many steps, then extract")
+    mode.add_argument("--ckpt", help="state_dict of an NGP(scale, max_res) model")
+    ap.add_argument("--resolution", type=int, default=128, help="cells per axis")
+    ap.add_argument("--threshold", type=float, default=None, help="density level (default: the occupancy threshold 0.01 * 1024 / sqrt(3))")
+    ap.add_argument("--normals", default="grid", choices=["grid", "analytic", "none"])
+    ap.add_argument("--out", default="mesh.ply", help=".ply or .obj")
+    ap.add_argument("--scale", type=float, default=0.5)
+    # the --sdf fit (fit_sdf_eikonal.py's options); --max_res also sizes the NGP of --ckpt
+    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--n", type=int, default=16384)
+    ap.add_argument("--log2_T", type=int, default=19)
+    ap.add_argument("--levels", type=int, default=16)
+    ap.add_argument("--max_res", type=float, default=None)
+    ap.add_argument("--width", type=int, default=64)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--eikonal_weight", type=float, default=0.1)
+    ap.add_argument("--seed", type=int, default=7)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("this example needs the GPU: libngp_hip has no CPU path")
+    if not args.out.endswith((".ply", ".obj")):
+        raise SystemExit("--out must end in .ply or .obj")
+    dev = torch.device("cuda")
+    from ngp_hip import mesh
+    normals = None if args.normals == "none" else args.normals
+    info = {}
+    t0 = time.time()
+    if args.sdf:
+        if normals == "analytic":
+            raise SystemExit("--normals analytic needs a model (--train_steps or --ckpt)")
+        if args.max_res is None:
+            args.max_res = 2048.0
+        fn, last = fit_sphere_sdf(args, dev)
+        info.update(mode="sdf", fit_steps=args.steps, sdf_loss_last=last)
+        torch.cuda.synchronize()
+        t1 = time.time()
+        msh, grid = mesh.extract_mesh(fn, args.resolution, 0.0 if args.threshold is None else args.threshold,
+                                      bounds=((0.0, 0.0, 0.0), (1.0, 1.0, 1.0)), normals=normals, sign=-1, return_grid=True)
+    else:
+        from modules.networks import NGP
+        from modules.rendering import MAX_SAMPLES
+        thr = 0.01 * MAX_SAMPLES / 3**0.5 if args.threshold is None else args.threshold
+        if args.ckpt:
+            model = NGP(scale=args.scale, max_res=1024 if args.max_res is None else int(args.max_res)).to(dev)
+            sd = torch.load(args.ckpt, map_location=dev)
+            sd = sd.get("state_dict", sd)
+            model.load_state_dict({k[6:] if k.startswith("model.") else k: v for k, v in sd.items()})
+            info.update(mode="ckpt")
+        else:
+            model, _ = train_procedural_model(args.train_steps, dev)
+            info.update(mode="procedural scene", train_steps=args.train_steps)
+        model.eval()
+        torch.cuda.synchronize()
+        t1 = time.time()
+        with torch.autocast("cuda", dtype=torch.float16):                  # the evaluation loops' numerics: density runs the fused kernels
+            msh, grid = mesh.extract_mesh(model, args.resolution, thr, normals=normals, return_grid=True)
+        info.update(threshold=thr)
+    torch.cuda.synchronize()
+    t2 = time.time()
+    (mesh.write_ply if args.out.endswith(".ply") else mesh.write_obj)(args.out, msh)
+    t3 = time.time()
+    info.update(mesh.topology(msh))
+    info.update(resolution=args.resolution, normals=args.normals, out=args.out, prepare_seconds=t1 - t0, extract_seconds=t2 - t1,
+                write_seconds=t3 - t2)
+    print(json.dumps(info))
+    info.update(mesh=msh, grid=grid)
+    return info
+
+
+if __name__ == "__main__":
+    main()

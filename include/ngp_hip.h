@@ -674,6 +674,26 @@ int ngp_deploy_render(const float* rays_o, const float* rays_d, const uint8_t* d
                       int max_samples, float T_threshold, float* rgb, float* opacity, float* depth, int32_t* n_samples, float* t_last,
                       void* stream);
 
+/* ---- isosurface extraction: marching tetrahedra on a sampled scalar field (csrc/mesh.hip; contract: DESIGN.md section 3) ----------
+ * values: f32 [nx, ny, nz], z fastest, every n >= 2, nx ny nz < 2^31; grid point (i, j, k) sits at lo + (i, j, k) h.  A point is inside
+ * iff sign v > sign iso in f32 (sign +1: a density, -1: a signed distance; NaN and v == iso are outside).  Each cell is split into the six
+ * Kuhn tetrahedra; a vertex lies on each lattice edge p -> p + d, d in {0,1}^3 \ {0}, whose ends differ, at t = (iso - v_p) / (v_q - v_p)
+ * (0.5 where that is not in [0, 1]), position lo + (float(i) + t d) h per axis.  Vertices are ordered by owner p, then by edge type
+ * 4 dx + 2 dy + dz; faces by cell, tetrahedron (axis permutations, lexicographic) and the listed order, counter-clockwise seen from the
+ * outside.  No atomics: the same input gives the same bytes.
+ * workspace_bytes: the size of `workspace` for this grid (about 4 bytes per point), -1 for a grid the other two refuse
+ * count : fills the workspace and writes counts[2] = {vertices, faces} on the device ({-1, -1} if either passes 2^31 - 1)
+ * emit  : after count on the same values, iso, sign and workspace: vertices f32 [V,3], faces int32 [T,3] and, unless NULL, normals f32
+ *         [V,3]: the central-difference gradient of the grid (one-sided on the boundary faces), interpolated along the edge with the same
+ *         t, times -sign, normalised; (0, 0, 0) where it is zero or not finite.  lo, h: three HOST floats each, h > 0.
+ * Both return -1 without a launch for a null required pointer, an n < 2, a sign other than +1 / -1, nx ny nz >= 2^31 or an h <= 0. */
+long long ngp_mesh_workspace_bytes(int nx, int ny, int nz);
+int ngp_mesh_count(const float* values, int nx, int ny, int nz, float iso, int sign, void* workspace, int32_t* counts /*[2]*/,
+                   void* stream);
+int ngp_mesh_emit(const float* values, int nx, int ny, int nz, float iso, int sign, const float* lo /*[3], host*/,
+                  const float* h /*[3], host*/, const void* workspace, float* vertices, float* normals /* may be NULL */, int32_t* faces,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

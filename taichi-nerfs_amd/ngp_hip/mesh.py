@@ -1,0 +1,154 @@
+"""Isosurface meshes from the models: sample a scalar field on a regular grid, run marching tetrahedra on the device
+(csrc/mesh.hip through ops.mesh_count / ops.mesh_emit), write the result as .ply or .obj.
+
+    mesh = extract_mesh(model, resolution=256, threshold=0.01 * 1024 / 3**0.5)        # NGP (any encoder) or VoxelGrid
+    mesh = extract_mesh(sdf_fn, 128, 0.0, bounds=((0, 0, 0), (1, 1, 1)), sign=-1)      # any callable points [n,3] -> values [n]
+    write_ply("scene.ply", mesh)
+
+The mesh is indexed (shared vertices), deterministic (the same grid gives the same bytes) and, wherever the surface stays off the grid
+boundary, a closed consistently oriented 2-manifold; the exact contract is in DESIGN.md section 3.  The extraction itself costs one host
+read (the vertex and face counts, to size the outputs)."""
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+class Mesh(NamedTuple):
+    vertices: torch.Tensor                  # [V,3] f32
+    faces: torch.Tensor                     # [T,3] int32, counter-clockwise seen from the outside
+    normals: Optional[torch.Tensor]         # [V,3] f32 unit vectors pointing out of the solid (0 where undefined), or None
+
+
+def marching_tetrahedra(values, iso, sign=+1, lo=(0.0, 0.0, 0.0), h=(1.0, 1.0, 1.0), normals=True):
+    """values: device f32 [Nx, Ny, Nz] sampled at lo + (i, j, k) * h; inside is sign * value > sign * iso (+1: a density, -1: a signed
+    distance).  normals=True adds the normalised central-difference gradient of the grid, pointing outwards.  An empty surface returns
+    empty tensors without an emit launch."""
+    workspace, counts = ops.mesh_count(values, iso, sign)
+    n_vertices, n_faces = counts.tolist()                               # the one synchronisation: the outputs' sizes
+    v, n, f = ops.mesh_emit(values, iso, sign, lo, h, workspace, n_vertices, n_faces, normals=bool(normals))     # checks lo and h
+    return Mesh(v, f, n)
+
+
+def _resolution3(resolution):
+    r = (resolution,) * 3 if np.isscalar(resolution) else tuple(resolution)
+    if len(r) != 3 or any(int(x) != x or x < 1 for x in r):
+        raise ValueError("resolution must be a positive integer or three of them (cells per axis), got %r" % (resolution,))
+    return tuple(int(x) for x in r)
+
+
+def grid_spacing(lo, hi, resolution):
+    """(lo, h) as python floats: `resolution` cells per axis between lo and hi, so resolution + 1 points."""
+    r = _resolution3(resolution)
+    lo, hi = [float(x) for x in lo], [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3 or not all(b > a for a, b in zip(lo, hi)):
+        raise ValueError("bounds must be lo[3] < hi[3], got %r, %r" % (lo, hi))
+    return lo, [(b - a) / n for a, b, n in zip(lo, hi, r)]
+
+
+def grid_points(lo, h, shape, start, stop, device):
+    """Positions [stop - start, 3] (f32) of the grid points with linear indices start .. stop - 1, z fastest: lo + (i, j, k) * h, the
+    product and the sum each rounded to f32 -- what sample_grid evaluates and what the extraction places the vertices between."""
+    _, ny, nz = shape
+    idx = torch.arange(start, stop, device=device, dtype=torch.int64)
+    ijk = torch.stack([idx // (ny * nz), idx // nz % ny, idx % nz], 1).to(torch.float32)
+    lo_t = torch.tensor(lo, device=device, dtype=torch.float32)
+    h_t = torch.tensor(h, device=device, dtype=torch.float32)
+    return lo_t + ijk * h_t
+
+
+def sample_grid(fn, lo, hi, resolution, chunk=2**21, device="cuda"):
+    """fn(points [n,3]) -> [n] evaluated on the (resolution + 1)^3 points between lo and hi, `chunk` points per call (it need not
+    divide the point count), under torch.no_grad() and in the caller's autocast state -> f32 [Rx+1, Ry+1, Rz+1] on `device`."""
+    lo, h = grid_spacing(lo, hi, resolution)
+    shape = tuple(n + 1 for n in _resolution3(resolution))
+    total = shape[0] * shape[1] * shape[2]
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be positive")
+    values = torch.empty(total, device=device, dtype=torch.float32)
+    with torch.no_grad():
+        for start in range(0, total, chunk):
+            stop = min(start + chunk, total)
+            out = fn(grid_points(lo, h, shape, start, stop, device))
+            if out.numel() != stop - start:
+                raise ValueError("fn must return one value per point, got %s for %d points" % (tuple(out.shape), stop - start))
+            values[start:stop] = out.reshape(-1).to(torch.float32)
+    return values.view(shape)
+
+
+def extract_mesh(model, resolution, threshold, bounds=None, normals="grid", return_grid=False, sign=+1, chunk=2**21, device=None):
+    """The surface density == threshold of `model` (NGP with any encoder, VoxelGrid: model.density, solid where the density is higher),
+    or the surface value == threshold of a plain callable points [n,3] -> [n] (sign=-1 for a signed distance; bounds are then required).
+    bounds: (lo[3], hi[3]), default the model's [xyz_min, xyz_max]; resolution: cells per axis.
+    normals: "grid" -- central differences of the sampled grid; "analytic" -- model.density_normals at the vertices (hash-grid NGP only:
+    the other models raise its NotImplementedError); None -- no normals.  return_grid=True also returns the sampled values."""
+    if normals not in ("grid", "analytic", None):
+        raise ValueError('normals must be "grid", "analytic" or None, got %r' % (normals,))
+    is_model = hasattr(model, "density")
+    fn = model.density if is_model else model
+    if normals == "analytic" and not hasattr(model, "density_normals"):
+        raise ValueError('normals="analytic" needs a model with density_normals')
+    if bounds is None:
+        if not (is_model and hasattr(model, "xyz_min") and hasattr(model, "xyz_max")):
+            raise ValueError("bounds=(lo, hi) is required for a plain callable")
+        bounds = (model.xyz_min.reshape(3).tolist(), model.xyz_max.reshape(3).tolist())
+    if device is None:
+        device = model.xyz_min.device if is_model and hasattr(model, "xyz_min") else "cuda"
+    lo, h = grid_spacing(bounds[0], bounds[1], resolution)
+    values = sample_grid(fn, bounds[0], bounds[1], resolution, chunk=chunk, device=device)
+    mesh = marching_tetrahedra(values, threshold, sign=sign, lo=lo, h=h, normals=normals == "grid")
+    if normals == "analytic":
+        n = model.density_normals(mesh.vertices)[1] if mesh.vertices.shape[0] else mesh.vertices.clone()
+        mesh = Mesh(mesh.vertices, mesh.faces, n)
+    return (mesh, values) if return_grid else mesh
+
+
+def topology(mesh):
+    """Host-side invariants of a mesh: dict(vertices, faces, euler = V - E + T, boundary_edges = edges used by one face only).  A closed
+    surface has no boundary edges; a sphere has euler 2, a torus 0."""
+    f = torch.as_tensor(mesh.faces).detach().cpu().numpy().astype(np.int64).reshape(-1, 3)
+    n_vertices = int(torch.as_tensor(mesh.vertices).shape[0])
+    e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), 1)
+    _, uses = np.unique(e[:, 0] * max(n_vertices, 1) + e[:, 1], return_counts=True)
+    return {"vertices": n_vertices, "faces": int(len(f)), "euler": n_vertices - int(len(uses)) + int(len(f)),
+            "boundary_edges": int((uses == 1).sum())}
+
+
+# ---- files (host code) -------------------------------------------------------------------------------------------------------------
+def _host(mesh):
+    v = np.ascontiguousarray(torch.as_tensor(mesh.vertices).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
+    f = np.ascontiguousarray(torch.as_tensor(mesh.faces).detach().cpu().numpy(), dtype="<i4").reshape(-1, 3)
+    n = None if mesh.normals is None else np.ascontiguousarray(torch.as_tensor(mesh.normals).detach().cpu().numpy(), dtype="<f4").reshape(-1, 3)
+    if n is not None and n.shape != v.shape:
+        raise ValueError("normals must be [V,3] like the vertices")
+    return v, f, n
+
+
+def write_ply(path, mesh):
+    """Binary little-endian PLY: float x y z (+ nx ny nz when the mesh has normals) per vertex, uchar 3 + three int32 per face."""
+    v, f, n = _host(mesh)
+    props = ["x", "y", "z"] + (["nx", "ny", "nz"] if n is not None else [])
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v)] + ["property float %s" % p for p in props] \
+        + ["element face %d" % len(f), "property list uchar int vertex_indices", "end_header"]
+    rows = np.empty(len(f), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    rows["n"], rows["idx"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write((v if n is None else np.concatenate([v, n], 1)).astype("<f4").tobytes())
+        fh.write(rows.tobytes())
+
+
+def write_obj(path, mesh):
+    """Wavefront OBJ: v (and vn) lines with nine significant digits (an f32 survives the round trip), 1-based f lines."""
+    v, f, n = _host(mesh)
+    with open(path, "w") as fh:
+        fh.write("# %d vertices, %d faces\n" % (len(v), len(f)))
+        fh.writelines("v %.9g %.9g %.9g\n" % tuple(r) for r in v.tolist())
+        if n is not None:
+            fh.writelines("vn %.9g %.9g %.9g\n" % tuple(r) for r in n.tolist())
+            fh.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist())
+        else:
+            fh.writelines("f %d %d %d\n" % tuple(r) for r in (f + 1).tolist())

@@ -744,6 +744,56 @@ def distortion_bwd(dL_dloss, ws, deltas, ts, ws_inc, wts_inc, rays_a):
     return dL_dws
 
 
+# ---------------------------------------------------------------------------------------------------- isosurface extraction
+def _mesh_grid(values, sign):
+    """Shape and sign checks first (they need no device), then the device check."""
+    if values.dim() != 3 or min(values.shape) < 2:
+        raise ValueError("values must be [Nx, Ny, Nz] with every N >= 2, got %s" % (tuple(values.shape),))
+    if values.numel() >= 2**31:
+        raise ValueError("values holds %d points; the extraction indexes them with int32 (< 2^31)" % values.numel())
+    if sign not in (1, -1):
+        raise ValueError("sign must be +1 (inside = above iso, a density) or -1 (inside = below iso, a signed distance), got %r" % (sign,))
+    _dev(values, torch.float32, "values")
+    return tuple(int(s) for s in values.shape)
+
+
+def mesh_count(values, iso, sign=1, workspace=None):
+    """First phase of marching tetrahedra on values [Nx, Ny, Nz] (csrc/mesh.hip): -> (workspace uint8 [ngp_mesh_workspace_bytes],
+    counts int32 [2] = {vertices, faces}, ON THE DEVICE).  The workspace is what mesh_emit needs; pass one back in to reuse it."""
+    nx, ny, nz = _mesh_grid(values, sign)
+    need = _lib().ngp_mesh_workspace_bytes(nx, ny, nz)
+    if workspace is None:
+        workspace = torch.empty(need, device=values.device, dtype=torch.uint8)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise ValueError("workspace must be a contiguous device uint8 buffer of at least %d bytes" % need)
+    counts = torch.empty(2, device=values.device, dtype=torch.int32)
+    check(_lib().ngp_mesh_count(_ptr(values), nx, ny, nz, float(iso), int(sign), _ptr(workspace), _ptr(counts), _stream()),
+          "ngp_mesh_count")
+    return workspace, counts
+
+
+def mesh_emit(values, iso, sign, lo, h, workspace, n_vertices, n_faces, normals=True):
+    """Second phase, after mesh_count on the same values, iso and sign: -> (vertices f32 [V,3], normals f32 [V,3] or None, faces int32
+    [T,3]).  n_vertices, n_faces: the host copies of mesh_count's counts.  lo, h: three floats each, h > 0."""
+    lo, h = [float(x) for x in lo], [float(x) for x in h]
+    if len(lo) != 3 or len(h) != 3 or not all(x > 0 for x in h):
+        raise ValueError("lo and h must hold three floats each and every h must be positive, got lo=%r h=%r" % (lo, h))
+    nx, ny, nz = _mesh_grid(values, sign)
+    if n_vertices < 0 or n_faces < 0:
+        raise ValueError("the mesh has more than 2^31 - 1 vertices or faces: extract it in parts")
+    _dev(workspace, torch.uint8, "workspace")
+    if workspace.numel() < _lib().ngp_mesh_workspace_bytes(nx, ny, nz):
+        raise ValueError("workspace is smaller than ngp_mesh_workspace_bytes of this grid")
+    vertices = torch.empty(n_vertices, 3, device=values.device, dtype=torch.float32)
+    faces = torch.empty(n_faces, 3, device=values.device, dtype=torch.int32)
+    nrm = torch.empty(n_vertices, 3, device=values.device, dtype=torch.float32) if normals else None
+    if n_vertices == 0 or n_faces == 0:                  # nothing to write: no launch
+        return vertices, nrm, faces
+    check(_lib().ngp_mesh_emit(_ptr(values), nx, ny, nz, float(iso), int(sign), (ctypes.c_float * 3)(*lo), (ctypes.c_float * 3)(*h),
+                               _ptr(workspace), _ptr(vertices), _ptr(nrm), _ptr(faces), _stream()), "ngp_mesh_emit")
+    return vertices, nrm, faces
+
+
 def levels_to_numpy(lv):
     """(scale, resolution, map_size, offset) as numpy arrays -- for tests and for the module buffers."""
     L = lv.n_levels
