@@ -619,6 +619,25 @@ int ngp_sample_rays(const float* poses /*[n_img,3,4]*/, const float* directions 
                     long long hw, const int64_t* img_idx, long long img0, const int64_t* pix_idx, int n, float* rays_o,
                     float* rays_d, float* rgb, void* stream);
 
+/* ---- f-5  ray and camera-pose gradients (pose refinement; csrc/ray_grad.hip).  First order; sums in a fixed
+ * order without float atomics: two launches give the same bytes, and a NaN stays inside its ray / image.
+ * march_train_bwd: adjoint of the sample write of ngp_march_train_write / ngp_march_train_fused (xyzs = o + t d, dirs = d), t held
+ *   constant.  Row m of rays_a is (ray_idx, start, N): d_rays_o[ray_idx] = sum_{j<N} d_xyzs[start+j],
+ *   d_rays_d[ray_idx] = sum_{j<N} ((ts[start+j] * d_xyzs[start+j]) + d_dirs[start+j]).  A NULL d_xyzs / d_dirs counts as zeros; N == 0
+ *   writes zeros; every output row named by a rays_a row is written, never accumulated (rows with ray_idx outside [0, n_rays) are
+ *   skipped).  Stated on rays_a rows: holds for the ray-ordered and the block-completion-ordered packing alike.
+ * sample_rays_bwd: adjoint of ngp_sample_rays / the one-pose form of ngp_get_rays, per image: d_poses[i][r][c] = sum_{k: img(k)=i}
+ *   d_rays_d[k][r] directions[pix(k)][c] (c < 3), d_poses[i][r][3] = sum_{k: img(k)=i} d_rays_o[k][r]; img(k) = img_idx[k] (img0 when
+ *   NULL), pix(k) = pix_idx[k] (k when NULL).  All 12 n_img entries are written (an image without rays: zeros); a ray whose image lies
+ *   outside [0, n_img) is skipped.  A NULL d_rays_o / d_rays_d counts as zeros.  n == 0 is valid (all zeros).
+ * get_rays_bwd: the per-ray-pose form of ngp_get_rays (poses [n,3,4]): the outer product per ray, d_rays_o into column 3. */
+int ngp_march_train_bwd(const float* d_xyzs /*[S,3] | NULL*/, const float* d_dirs /*[S,3] | NULL*/, const float* ts /*[S]*/,
+                        const int32_t* rays_a /*[n,3]*/, int n_rays, float* d_rays_o /*[n,3]*/, float* d_rays_d /*[n,3]*/, void* stream);
+int ngp_sample_rays_bwd(const float* directions /*[hw,3]*/, const int64_t* img_idx /*[n] | NULL -> img0*/, long long img0,
+                        const int64_t* pix_idx /*[n] | NULL -> k*/, const float* d_rays_o /*[n,3] | NULL*/, const float* d_rays_d /*[n,3] | NULL*/,
+                        int n, int n_img, float* d_poses /*[n_img,3,4]*/, void* stream);
+int ngp_get_rays_bwd(const float* directions /*[n,3]*/, const float* d_rays_o, const float* d_rays_d, int n, float* d_poses /*[n,3,4]*/, void* stream);
+
 /* ---- f-3  occupancy-grid update without host round trips (modules/networks.py:181-209,255-290).
  * compact : list[0..count) = cells of ONE cascade with density > threshold, in cell order (deterministic); count is written
  * sample  : m uniform cells (u_cell [m] in [0,1) -> Morton code) + m picks from the list (u_pick [m]) -> Morton indices [2m] and jittered

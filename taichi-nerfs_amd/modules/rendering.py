@@ -101,10 +101,32 @@ def _background(exp_step_factor, device):
     return torch.ones(3, device=device) if exp_step_factor == 0 else torch.zeros(3, device=device)
 
 
+def _ray_grad_wanted(rays_o, rays_d):
+    return torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+
+
+def _check_position_gradient(model):
+    """Rays that require grad need d(sigma, rgb)/dx of the model: the hash encoder has it, the tri-plane encoder and the voxel grid do
+    not.  Any other callable passes: autograd decides what reaches xyzs."""
+    from .networks import NGP, VoxelGrid
+    if isinstance(model, NGP) and model.pos_encoder_type != 'hash':
+        raise NotImplementedError("render() with rays that require grad needs the hash encoder's position gradient; pos_encoder_type=%r "
+                                  "has none yet" % (model.pos_encoder_type,))
+    if isinstance(model, VoxelGrid):
+        raise NotImplementedError("render() with rays that require grad needs a position gradient; the voxel-grid model (svox) has "
+                                  "none yet")
+
+
 def render(model, rays_o, rays_d, test_time=False, exp_step_factor=0, T_threshold=1e-4, max_samples=MAX_SAMPLES):
-    """rays_o, rays_d: [N,3].  Returns the reference's result dictionary (rgb, depth, opacity, ...)."""
+    """rays_o, rays_d: [N,3].  Returns the reference's result dictionary (rgb, depth, opacity, ...).
+
+    Training rays that require grad (pose refinement: ngp_hip.rays / ngp_hip.poses) leave the fused whole-render node for
+    march -> model(xyzs, dirs) -> model.render_func, whose march carries d_xyzs / d_dirs back to the rays (ngp_march_train_bwd)."""
     rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()      # geometry is fp32 (ray_utils.py:50)
-    if not test_time and getattr(model, 'fused_train_ok', None) is not None and model.fused_train_ok(rays_o):
+    ray_grad = not test_time and _ray_grad_wanted(rays_o, rays_d)
+    if ray_grad:
+        _check_position_gradient(model)
+    if not test_time and not ray_grad and getattr(model, 'fused_train_ok', None) is not None and model.fused_train_ok(rays_o):
         # the fused training render does the slab test of intersection.py:22-37 inside its march launch (same arithmetic, same hits_t)
         return _render_rays_train(model, rays_o, rays_d, None, exp_step_factor, T_threshold)
     hits_t = ray_aabb_intersection(rays_o, rays_d, model.scale)
@@ -188,7 +210,8 @@ def _render_rays_test_oneshot(model, rays_o, rays_d, hits_t, exp_step_factor, T_
 
 def _render_rays_train(model, rays_o, rays_d, hits_t, exp_step_factor, T_threshold):
     """march (occupancy-skipping, jittered) -> shade -> differentiable front-to-back compositing."""
-    if getattr(model, 'fused_train_ok', None) is not None and model.fused_train_ok(rays_o):
+    if (not _ray_grad_wanted(rays_o, rays_d) and getattr(model, 'fused_train_ok', None) is not None
+            and model.fused_train_ok(rays_o)):
         # one autograd node, no host sync; the per-sample outputs stay in the N*MAX_SAMPLES arena until somebody reads them
         # through the result dictionary (TrainResults: reference-shaped [S] tensors on first access)
         from ngp_hip.fused import FusedTrainRender, RenderConfig, TrainArena

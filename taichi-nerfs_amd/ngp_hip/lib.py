@@ -16,7 +16,8 @@ CSRC = os.path.join(PKG_ROOT, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
 LIB_PATH = os.path.join(CSRC, "libngp_hip.so")
 SOURCES = ["march.hip", "hash_grid.hip", "hash_bwd_lds.hip", "composite.hip", "sh_grid.hip", "mlp.hip", "optim.hip", "distortion.hip", "occupancy.hip", "rays.hip",
-           "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip", "hash_grad_input.hip", "hash_grad_input2.hip", "mesh.hip"]
+           "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip", "hash_grad_input.hip", "hash_grad_input2.hip", "mesh.hip",
+           "ray_grad.hip"]
 HEADERS = ["ngp_device.h", "hash_common.h", "hash_lanes.h", "march_common.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 FLAGS_STAMP = LIB_PATH + ".flags"      # the flags the in-tree .so was built with: a flag change rebuilds
@@ -255,6 +256,9 @@ SIGNATURES = {
     "ngp_get_rays": [_P, _P, _I, _I, _P, _P, _P],
     "ngp_stage_batch": [_P, _P, _P, _P, _P, _P, _I, _P],
     "ngp_sample_rays": [_P, _P, _P, _I, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _I, _P, _P, _P, _P],
+    "ngp_march_train_bwd": [_P, _P, _P, _P, _I, _P, _P, _P],
+    "ngp_sample_rays_bwd": [_P, _P, ctypes.c_longlong, _P, _P, _P, _I, _I, _P, _P],
+    "ngp_get_rays_bwd": [_P, _P, _P, _I, _P, _P],
     "ngp_occ_compact": [_P, _F, _I, _P, _P, _P, _P],
     "ngp_sorted_uniforms": [_P, _I, _I, _P, _P, _P],
     "ngp_occ_sample": [_P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P],

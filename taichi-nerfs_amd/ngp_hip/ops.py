@@ -178,6 +178,65 @@ def rng_uniform(seed, n, device="cuda"):
     return out
 
 
+def march_train_bwd(d_xyzs, d_dirs, ts, rays_a):
+    """ngp_march_train_bwd: adjoint of xyzs = o + t d, dirs = d over the rows (ray_idx, start, N) of rays_a, t held constant.
+    d_xyzs, d_dirs: [S,3] float32 or None (= zeros); ts [S]; rays_a [n,3] of march_train / march_train_fused, whose rows must
+    address samples inside [0, S).  -> (d_rays_o, d_rays_d) [n,3], every row written, indexed by ray_idx."""
+    _dev(ts, torch.float32, "ts"); _dev(rays_a, torch.int32, "rays_a")
+    for name, t in (("d_xyzs", d_xyzs), ("d_dirs", d_dirs)):
+        if t is not None:
+            _dev(t, torch.float32, name)
+            if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] != ts.shape[0]:
+                raise ValueError("%s must be [S,3] with S = len(ts) = %d, got %s" % (name, ts.shape[0], tuple(t.shape)))
+    n = rays_a.shape[0]
+    d_rays_o = torch.empty(n, 3, device=rays_a.device, dtype=torch.float32)
+    d_rays_d = torch.empty(n, 3, device=rays_a.device, dtype=torch.float32)
+    check(_lib().ngp_march_train_bwd(_ptr(d_xyzs), _ptr(d_dirs), _ptr(ts), _ptr(rays_a), n, _ptr(d_rays_o), _ptr(d_rays_d),
+                                     _stream()), "ngp_march_train_bwd")
+    return d_rays_o, d_rays_d
+
+
+def sample_rays_bwd(directions, img_idx, img0, pix_idx, d_rays_o, d_rays_d, n_img):
+    """ngp_sample_rays_bwd: d_poses [n_img,3,4] of the rays of ngp_sample_rays (or of get_rays with one pose: img_idx = None,
+    img0 = 0, pix_idx = None, n_img = 1).  img_idx / pix_idx: [n] int64 or None (every ray from image img0 / pixel k of ray k);
+    d_rays_o / d_rays_d: [n,3] float32 or None (= zeros), at least one given.  pix_idx must address rows of directions."""
+    _dev(directions, torch.float32, "directions")
+    grads = [g for g in (d_rays_o, d_rays_d) if g is not None]
+    if not grads:
+        raise ValueError("sample_rays_bwd needs d_rays_o or d_rays_d")
+    n = grads[0].shape[0]
+    for name, t in (("d_rays_o", d_rays_o), ("d_rays_d", d_rays_d)):
+        if t is not None:
+            _dev(t, torch.float32, name)
+            if tuple(t.shape) != (n, 3):
+                raise ValueError("%s must be [%d,3], got %s" % (name, n, tuple(t.shape)))
+    for name, t in (("img_idx", img_idx), ("pix_idx", pix_idx)):
+        if t is not None:
+            _dev(t, torch.int64, name)
+            if tuple(t.shape) != (n,):
+                raise ValueError("%s must be [%d], got %s" % (name, n, tuple(t.shape)))
+    if pix_idx is None and directions.shape[0] < n:
+        raise ValueError("without pix_idx ray k reads directions[k]: %d directions for %d rays" % (directions.shape[0], n))
+    d_poses = torch.empty(int(n_img), 3, 4, device=directions.device, dtype=torch.float32)
+    check(_lib().ngp_sample_rays_bwd(_ptr(directions), _ptr(img_idx), ctypes.c_longlong(int(img0)), _ptr(pix_idx), _ptr(d_rays_o),
+                                     _ptr(d_rays_d), n, int(n_img), _ptr(d_poses), _stream()), "ngp_sample_rays_bwd")
+    return d_poses
+
+
+def get_rays_bwd(directions, d_rays_o, d_rays_d):
+    """ngp_get_rays_bwd: d_poses [n,3,4] of get_rays with one pose per ray; d_rays_o / d_rays_d [n,3] float32 or None (= zeros)."""
+    _dev(directions, torch.float32, "directions")
+    n = directions.shape[0]
+    for name, t in (("d_rays_o", d_rays_o), ("d_rays_d", d_rays_d)):
+        if t is not None:
+            _dev(t, torch.float32, name)
+            if tuple(t.shape) != (n, 3):
+                raise ValueError("%s must be [%d,3], got %s" % (name, n, tuple(t.shape)))
+    d_poses = torch.empty(n, 3, 4, device=directions.device, dtype=torch.float32)
+    check(_lib().ngp_get_rays_bwd(_ptr(directions), _ptr(d_rays_o), _ptr(d_rays_d), n, _ptr(d_poses), _stream()), "ngp_get_rays_bwd")
+    return d_poses
+
+
 # ---------------------------------------------------------------------------------------------------- a-3
 def march_test(rays_o, rays_d, hits_t, alive_indices, density_bitfield, cascades, scale, exp_step_factor, grid_size,
                max_samples):

@@ -11,7 +11,7 @@ import torch
 
 from . import lib as _lib_mod
 from .lib import check
-from .ops import _dev, _ptr, _stream
+from .ops import _dev, _ptr, _stream, get_rays_bwd, sample_rays_bwd
 
 
 def get_ray_directions(H, W, K, device='cpu', random=False, return_uv=False, flatten=True):
@@ -31,9 +31,64 @@ def get_ray_directions(H, W, K, device='cpu', random=False, return_uv=False, fla
     return (directions, grid) if return_uv else directions
 
 
+def _get_rays(directions, c2w):
+    n = directions.shape[0]
+    rays_o = torch.empty(n, 3, device=directions.device, dtype=torch.float32)
+    rays_d = torch.empty(n, 3, device=directions.device, dtype=torch.float32)
+    check(_lib_mod.load().ngp_get_rays(_ptr(directions), _ptr(c2w), int(c2w.ndim == 3), n, _ptr(rays_o), _ptr(rays_d), _stream()),
+          "ngp_get_rays")
+    return rays_o, rays_d
+
+
+def _grad_arg(g):
+    return None if g is None else g.contiguous().float()
+
+
+class _GetRays(torch.autograd.Function):
+    """get_rays with a gradient for c2w (not for directions): one pose -> ngp_sample_rays_bwd over one image, a pose per ray ->
+    ngp_get_rays_bwd."""
+
+    @staticmethod
+    def forward(ctx, directions, c2w):
+        ctx.save_for_backward(directions)
+        ctx.per_ray = c2w.ndim == 3
+        ctx.set_materialize_grads(False)
+        return _get_rays(directions, c2w)
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        if g_o is None and g_d is None:
+            return None, None
+        (directions,) = ctx.saved_tensors
+        g_o, g_d = _grad_arg(g_o), _grad_arg(g_d)
+        if ctx.per_ray:
+            return None, get_rays_bwd(directions, g_o, g_d)
+        return None, sample_rays_bwd(directions, None, 0, None, g_o, g_d, 1)[0]
+
+
+class _SampleRays(torch.autograd.Function):
+    """RayBatcher.sample on poses that require grad: rays_o / rays_d carry the graph, their backward is one ngp_sample_rays_bwd."""
+
+    @staticmethod
+    def forward(ctx, poses, batcher, img_idxs, img0, pix_idxs):
+        rays_o, rays_d, rgb = batcher._launch(poses, img_idxs, img0, pix_idxs)
+        ctx.save_for_backward(batcher.directions, img_idxs, pix_idxs)
+        ctx.img0, ctx.n_img = img0, poses.shape[0]
+        ctx.mark_non_differentiable(rgb)
+        ctx.set_materialize_grads(False)
+        return rays_o, rays_d, rgb
+
+    @staticmethod
+    def backward(ctx, g_o, g_d, _g_rgb):
+        if g_o is None and g_d is None:
+            return (None,) * 5
+        directions, img_idxs, pix_idxs = ctx.saved_tensors
+        return (sample_rays_bwd(directions, img_idxs, ctx.img0, pix_idxs, _grad_arg(g_o), _grad_arg(g_d), ctx.n_img),) + (None,) * 4
+
+
 def get_rays(directions, c2w):
     """directions [N,3] (camera frame), c2w [3,4] or [N,3,4] -> rays_o, rays_d [N,3] float32 in world coordinates
-    (ray_utils.py:51-80).  Device tensors only."""
+    (ray_utils.py:51-80).  Device tensors only.  Differentiable with respect to c2w (both forms); directions get no gradient."""
     directions = directions.contiguous().float()
     c2w = c2w.float()
     if c2w.shape[-1] == 4 and c2w.shape[-2] == 4:                       # homogeneous 4x4 poses: the reference drops the last row
@@ -44,11 +99,9 @@ def get_rays(directions, c2w):
     per_ray = c2w.ndim == 3
     if per_ray and c2w.shape[0] != n:
         raise ValueError("per-ray poses need one [3,4] matrix per direction")
-    rays_o = torch.empty(n, 3, device=directions.device, dtype=torch.float32)
-    rays_d = torch.empty(n, 3, device=directions.device, dtype=torch.float32)
-    check(_lib_mod.load().ngp_get_rays(_ptr(directions), _ptr(c2w), int(per_ray), n, _ptr(rays_o), _ptr(rays_d), _stream()),
-          "ngp_get_rays")
-    return rays_o, rays_d
+    if torch.is_grad_enabled() and c2w.requires_grad:
+        return _GetRays.apply(directions.detach(), c2w)
+    return _get_rays(directions, c2w)
 
 
 class RayBatcher:
@@ -73,22 +126,40 @@ class RayBatcher:
     def __len__(self):
         return self.poses.shape[0]
 
-    def sample(self, idx=None, generator=None):
+    def _launch(self, poses, img_idxs, img0, pix_idxs):
+        n = pix_idxs.shape[0]
+        f32 = dict(device=pix_idxs.device, dtype=torch.float32)
+        rays_o, rays_d, rgb = torch.empty(n, 3, **f32), torch.empty(n, 3, **f32), torch.empty(n, 3, **f32)
+        check(self.L.ngp_sample_rays(_ptr(poses), _ptr(self.directions), _ptr(self.rays), self.rays.shape[2],
+                                     ctypes.c_longlong(self.rays.shape[1]), _ptr(img_idxs), ctypes.c_longlong(img0), _ptr(pix_idxs), n,
+                                     _ptr(rays_o), _ptr(rays_d), _ptr(rgb), _stream()), "ngp_sample_rays")
+        return rays_o, rays_d, rgb
+
+    def sample(self, idx=None, generator=None, poses=None):
         """One training batch.  all_images: an image index per ray; same_image: every ray from image `idx` (drawn like
-        train.py:171 when None).  -> {'img_idxs', 'pix_idxs', 'rays_o', 'rays_d', 'rgb'} (device tensors)."""
+        train.py:171 when None).  -> {'img_idxs', 'pix_idxs', 'rays_o', 'rays_d', 'rgb'} (device tensors).
+
+        poses: optional [n_img,3,4] tensor that replaces self.poses for this batch (ngp_hip.poses.PoseRefiner's output); where it
+        requires grad, rays_o and rays_d carry the graph back to it (ngp_sample_rays_bwd)."""
         dev, n = self.rays.device, self.batch_size
         hw = self.rays.shape[1]
         if self.ray_sampling_strategy == 'all_images':
             img_idxs = torch.randint(0, len(self), (n,), device=dev, generator=generator)            # base.py:40-45
-            img_ptr, img0 = _ptr(img_idxs), 0
+            img_t, img0 = img_idxs, 0
         else:
             if idx is None:
                 idx = int(torch.randint(0, len(self), (1,)).item())                                   # train.py:171
-            img_idxs, img_ptr, img0 = idx, _ptr(None), int(idx)
+            img_idxs, img_t, img0 = idx, None, int(idx)
         pix_idxs = torch.randint(0, hw, (n,), device=dev, generator=generator)                       # base.py:51-53
-        f32 = dict(device=dev, dtype=torch.float32)
-        rays_o, rays_d, rgb = torch.empty(n, 3, **f32), torch.empty(n, 3, **f32), torch.empty(n, 3, **f32)
-        check(self.L.ngp_sample_rays(_ptr(self.poses), _ptr(self.directions), _ptr(self.rays), self.rays.shape[2],
-                                     ctypes.c_longlong(hw), img_ptr, ctypes.c_longlong(img0), _ptr(pix_idxs), n, _ptr(rays_o),
-                                     _ptr(rays_d), _ptr(rgb), _stream()), "ngp_sample_rays")
+        if poses is None:
+            rays_o, rays_d, rgb = self._launch(self.poses, img_t, img0, pix_idxs)
+        else:
+            poses = poses[..., :3, :].float().contiguous()
+            _dev(poses, torch.float32, "poses")
+            if poses.shape != self.poses.shape:
+                raise ValueError("poses must be [n_img,3,4] = %s, got %s" % (tuple(self.poses.shape), tuple(poses.shape)))
+            if torch.is_grad_enabled() and poses.requires_grad:
+                rays_o, rays_d, rgb = _SampleRays.apply(poses, self, img_t, img0, pix_idxs)
+            else:
+                rays_o, rays_d, rgb = self._launch(poses, img_t, img0, pix_idxs)
         return {'img_idxs': img_idxs, 'pix_idxs': pix_idxs, 'rays_o': rays_o, 'rays_d': rays_d, 'rgb': rgb}
