@@ -713,6 +713,41 @@ int ngp_mesh_emit(const float* values, int nx, int ny, int nz, float iso, int si
                   const float* h /*[3], host*/, const void* workspace, float* vertices, float* normals /* may be NULL */, int32_t* faces,
                   void* stream);
 
+/* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
+ * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
+ * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],
+ * thr = T_threshold, bg.
+ *     ic = -( relu(-c/2 + 1/2) (1 - r) + relu(-c) r )
+ *     h  = ic delta / 2
+ *     p  = sigmoid((f - h) s),  n = sigmoid((f + h) s),  sigmoid(x) = 1 / (1 + exp(-x))       (exp = inf gives 0, not NaN)
+ *     a  = clip( (p - n + 1e-5) / (p + 1e-5), 0, 1 )
+ *     T = 1;  stop at the first !(T > thr);  w = a T;  R += w rgb;  A += w aux;  D += w t;  O += w;  T <- T (1 - a);  M += 1
+ *     rgb_out = R + bg (1 - O)
+ * fwd writes total_samples[n] (= M), opacity[n], depth[n], rgb[n,3], rgb_out[n,3] (nullable), aux_out[n,3] (nullable; needs aux), all
+ * indexed by the ray index rays_a[.,0], and ws[S], alphas[S]: w_j and a_j of the live samples, exact +0 behind the live count.
+ * bwd takes the cotangents of opacity, depth, rgb (of rgb_out when bg != 0: the blend's share -bg sum_c dL_drgb is added to d opacity),
+ * aux_out and ws -- all but dL_drgb nullable --, the forward's inputs and its total_samples and alphas, and writes d_sdf[S], d_cos[S],
+ * d_rgbs[S,3], d_aux[S,3] (nullable) and d_inv_s[1].  With p' = p (1 - p), n' = n (1 - n), den = p + 1e-5, zero where the clip is active:
+ *     da/df = s [ p'(1-a) - n' ] / den                     da/dh = -s [ p'(1-a) + n' ] / den
+ *     da/dc = da/dh  delta/2  ( (1-r)/2 [-c/2+1/2 > 0] + r [-c > 0] )
+ *     da/ds = [ (f-h) p'(1-a) - (f+h) n' ] / den
+ * dL/da_j is the adjoint of the loop (a reverse sweep: finite when 1 - a_j is exactly 0) under the per-sample cotangent
+ * G_j = g_rgb . rgb_j + g_aux . aux_j + g_depth t_j + g_opacity' + g_ws[j].  delta and t get no gradient.  Samples behind the live
+ * count get exact +0 everywhere.  d_inv_s sums every live sample of the launch without atomics (per-ray rows in `workspace`, n_rays
+ * floats, then one block in a fixed order): the same inputs give the same bits.
+ * n_rays <= 0: returns 0 without a launch.  A ray with N == 0 writes zeros (rgb_out = bg).  A NaN sdf / cosv poisons its own ray only
+ * (and d_inv_s).  -1 for a null required pointer. */
+int ngp_surface_composite_fwd(const float* sdf, const float* cosv, const float* rgbs, const float* aux /* may be NULL */,
+                              const float* deltas, const float* ts, const int32_t* rays_a, const float* inv_s /* device, [1] */,
+                              float cos_anneal, float T_threshold, int n_rays, float bg, int32_t* total_samples, float* opacity,
+                              float* depth, float* rgb, float* rgb_out /* may be NULL */, float* aux_out /* may be NULL */, float* ws,
+                              float* alphas, void* stream);
+int ngp_surface_composite_bwd(const float* dL_dopacity, const float* dL_ddepth, const float* dL_drgb, const float* dL_daux,
+                              const float* dL_dws, const float* sdf, const float* cosv, const float* rgbs, const float* aux,
+                              const float* deltas, const float* ts, const int32_t* rays_a, const float* inv_s, float cos_anneal, int n_rays,
+                              float bg, const int32_t* total_samples, const float* alphas, float* d_sdf, float* d_cos, float* d_rgbs,
+                              float* d_aux /* may be NULL */, float* d_inv_s /* [1] */, float* workspace /* [n_rays] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -853,6 +853,75 @@ def mesh_emit(values, iso, sign, lo, h, workspace, n_vertices, n_faces, normals=
     return vertices, nrm, faces
 
 
+# ---------------------------------------------------------------------------------------------------- surface rendering
+def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
+    _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
+    _dev(deltas, torch.float32, "deltas"); _dev(ts, torch.float32, "ts"); _dev(rays_a, torch.int32, "rays_a")
+    _dev(inv_s, torch.float32, "inv_s")
+    S = sdf.numel()
+    if sdf.dim() != 1 or cosv.shape != sdf.shape or deltas.shape != sdf.shape or ts.shape != sdf.shape or tuple(rgbs.shape) != (S, 3):
+        raise ValueError("sdf, cosv, deltas, ts must be [S] and rgbs [S, 3]; got %s %s %s %s %s"
+                         % tuple(tuple(t.shape) for t in (sdf, cosv, deltas, ts, rgbs)))
+    if aux is not None:
+        _dev(aux, torch.float32, "aux")
+        if tuple(aux.shape) != (S, 3):
+            raise ValueError("aux must be [S, 3], got %s" % (tuple(aux.shape),))
+    if rays_a.dim() != 2 or rays_a.shape[1] != 3:
+        raise ValueError("rays_a must be [n_rays, 3], got %s" % (tuple(rays_a.shape),))
+    if inv_s.numel() != 1:
+        raise ValueError("inv_s must hold one float (it is read on the device), got %d" % inv_s.numel())
+    return S, rays_a.shape[0]
+
+
+def surface_composite_fwd(sdf, cosv, rgbs, deltas, ts, rays_a, inv_s, cos_anneal=1.0, T_threshold=1e-4, aux=None, bg=0.0):
+    """ngp_surface_composite_fwd (csrc/surface.hip; contract in include/ngp_hip.h): the NeuS-opacity compositor.
+    -> (total_samples [n] i32, opacity [n], depth [n], rgb [n,3], rgb_out [n,3] = rgb + bg (1 - opacity), aux_out [n,3] or None,
+    ws [S], alphas [S])."""
+    S, n = _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s)
+    dev = sdf.device
+    total_samples = torch.empty(n, device=dev, dtype=torch.int32)
+    opacity, depth = torch.empty(n, device=dev), torch.empty(n, device=dev)
+    rgb, rgb_out = torch.empty(n, 3, device=dev), torch.empty(n, 3, device=dev)
+    aux_out = torch.empty(n, 3, device=dev) if aux is not None else None
+    ws, alphas = torch.empty(S, device=dev), torch.empty(S, device=dev)
+    check(_lib().ngp_surface_composite_fwd(_ptr(sdf), _ptr(cosv), _ptr(rgbs), _ptr(aux), _ptr(deltas), _ptr(ts), _ptr(rays_a), _ptr(inv_s),
+                                           float(cos_anneal), float(T_threshold), n, float(bg), _ptr(total_samples), _ptr(opacity),
+                                           _ptr(depth), _ptr(rgb), _ptr(rgb_out), _ptr(aux_out), _ptr(ws), _ptr(alphas), _stream()),
+          "ngp_surface_composite_fwd")
+    return total_samples, opacity, depth, rgb, rgb_out, aux_out, ws, alphas
+
+
+def surface_composite_bwd(dL_dopacity, dL_ddepth, dL_drgb, dL_daux, dL_dws, sdf, cosv, rgbs, deltas, ts, rays_a, inv_s, total_samples, alphas,
+                          cos_anneal=1.0, aux=None, bg=0.0):
+    """ngp_surface_composite_bwd: -> (d_sdf [S], d_cos [S], d_rgbs [S,3], d_aux [S,3] or None, d_inv_s [1]).  Every cotangent but dL_drgb
+    may be None; dL_drgb is the gradient of rgb_out when bg != 0.  d_inv_s is summed without atomics: bit-reproducible."""
+    S, n = _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s)
+    if dL_drgb is None:
+        raise ValueError("dL_drgb is required")
+    for name, t, shape in (("dL_dopacity", dL_dopacity, (n,)), ("dL_ddepth", dL_ddepth, (n,)), ("dL_drgb", dL_drgb, (n, 3)),
+                           ("dL_daux", dL_daux, (n, 3)), ("dL_dws", dL_dws, (S,))):
+        if t is not None:
+            _dev(t, torch.float32, name)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must be %s, got %s" % (name, shape, tuple(t.shape)))
+    if dL_daux is not None and aux is None:
+        raise ValueError("dL_daux without aux")
+    _dev(total_samples, torch.int32, "total_samples"); _dev(alphas, torch.float32, "alphas")
+    if total_samples.numel() != n or alphas.numel() != S:
+        raise ValueError("total_samples must be [n_rays] and alphas [S]")
+    dev = sdf.device
+    d_sdf, d_cos, d_rgbs = torch.empty(S, device=dev), torch.empty(S, device=dev), torch.empty(S, 3, device=dev)
+    d_aux = torch.empty(S, 3, device=dev) if aux is not None else None
+    d_inv_s = torch.zeros(1, device=dev)
+    workspace = torch.empty(max(n, 1), device=dev)
+    check(_lib().ngp_surface_composite_bwd(_ptr(dL_dopacity), _ptr(dL_ddepth), _ptr(dL_drgb), _ptr(dL_daux), _ptr(dL_dws), _ptr(sdf),
+                                           _ptr(cosv), _ptr(rgbs), _ptr(aux), _ptr(deltas), _ptr(ts), _ptr(rays_a), _ptr(inv_s),
+                                           float(cos_anneal), n, float(bg), _ptr(total_samples), _ptr(alphas), _ptr(d_sdf), _ptr(d_cos),
+                                           _ptr(d_rgbs), _ptr(d_aux), _ptr(d_inv_s), _ptr(workspace), _stream()),
+          "ngp_surface_composite_bwd")
+    return d_sdf, d_cos, d_rgbs, d_aux, d_inv_s
+
+
 def levels_to_numpy(lv):
     """(scale, resolution, map_size, offset) as numpy arrays -- for tests and for the module buffers."""
     L = lv.n_levels

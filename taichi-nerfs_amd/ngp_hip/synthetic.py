@@ -11,6 +11,9 @@
 `procedural_field` / `procedural_render_gt`: an analytic "Lego-shape" scene (base plate, tower, studs inside
                [-0.35, 0.35]^3, white background) and its dense-integration renderer -- the scene-consistent target
                colours bench.py and examples/train_procedural.py train against.
+`surface_sdf` / `surface_render_gt` / `orbit_camera_rays`: an analytic SURFACE scene with a known signed distance (a sphere united
+               with a box inside [-0.5, 0.5]^3), its sphere-traced Lambert-shaded renderer and the camera ring
+               examples/train_surface.py trains an SDFField against.
 """
 import numpy as np
 
@@ -214,3 +217,77 @@ def ball_slab_bitfield(cascades, scale, grid_size=128, seed=23, ball_r=0.4, slab
         occ |= rng.random(G**3) < far_fraction
         out.append(occ)
     return np.packbits(np.concatenate(out), bitorder='little')
+
+
+# ---- analytic SURFACE scene with a known signed distance: a sphere united with a box, inside [-0.5, 0.5]^3 ---------------------
+SURFACE_SPHERE = ((-0.08, 0.0, 0.05), 0.22)                    # centre, radius
+SURFACE_BOX = ((0.16, 0.02, -0.08), (0.16, 0.2, 0.12))         # centre, half-size
+SURFACE_LIGHT = (0.35, -0.5, 0.79)                             # direction towards the light (normalised in the renderer)
+
+
+def surface_sdf(x):
+    """x: [...,3] torch tensor -> the exact signed distance [...] of the union (min of the two exact distances: exact outside, a
+    lower bound in magnitude inside, zero exactly on the surface)."""
+    import torch
+    c, r = SURFACE_SPHERE
+    ds = torch.linalg.norm(x - torch.tensor(c, device=x.device, dtype=x.dtype), dim=-1) - r
+    bc, bh = SURFACE_BOX
+    q = (x - torch.tensor(bc, device=x.device, dtype=x.dtype)).abs() - torch.tensor(bh, device=x.device, dtype=x.dtype)
+    db = torch.linalg.norm(q.clamp_min(0), dim=-1) + q.amax(-1).clamp_max(0)
+    return torch.minimum(ds, db)
+
+
+def surface_albedo(x):
+    """Striped albedo [...,3]: reddish on the sphere's side, bluish on the box's."""
+    import torch
+    c, r = SURFACE_SPHERE
+    on_sphere = (torch.linalg.norm(x - torch.tensor(c, device=x.device, dtype=x.dtype), dim=-1) - r) < 1e-3
+    stripe = 0.75 + 0.25 * torch.sin(30.0 * x.sum(-1, keepdim=True))
+    col = torch.where(on_sphere[..., None], torch.tensor((0.9, 0.35, 0.2), device=x.device, dtype=x.dtype),
+                      torch.tensor((0.2, 0.45, 0.9), device=x.device, dtype=x.dtype))
+    return col * stripe
+
+
+def surface_render_gt(rays_o, rays_d, n_steps=96, chunk=65536, bg=1.0, far=4.0):
+    """Sphere-traced, Lambert-shaded ground truth along rays [N,3] (torch, any device; directions of any length): march
+    t += sdf(o + t d) for n_steps, a hit is |sdf| < 1e-4 within `far`; the normal is the central difference of the SDF (step 1e-4), the
+    colour albedo * (0.3 + 0.7 max(n . l, 0)); misses show bg.  -> (rgb [N,3], hit [N] bool, depth [N], normal [N,3]), float32."""
+    import torch
+    out = [[], [], [], []]
+    with torch.no_grad():
+        light = torch.tensor(SURFACE_LIGHT, device=rays_o.device)
+        light = light / light.norm()
+        for i in range(0, rays_o.shape[0], chunk):
+            o, d = rays_o[i:i + chunk].float(), rays_d[i:i + chunk].float()
+            d = d / d.norm(dim=-1, keepdim=True)
+            t = torch.zeros(o.shape[0], device=o.device)
+            for _ in range(n_steps):
+                t = (t + surface_sdf(o + t[:, None] * d)).clamp_max(far)
+            x = o + t[:, None] * d
+            hit = (surface_sdf(x).abs() < 1e-4) & (t < far)
+            e = 1e-4 * torch.eye(3, device=o.device)
+            n = torch.stack([surface_sdf(x + e[k]) - surface_sdf(x - e[k]) for k in range(3)], -1)
+            n = n / n.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+            shade = 0.3 + 0.7 * (n * light).sum(-1, keepdim=True).clamp_min(0)
+            rgb = torch.where(hit[:, None], surface_albedo(x) * shade, torch.full_like(x, bg))
+            for lst, v in zip(out, (rgb, hit, torch.where(hit, t, torch.zeros_like(t)), n * hit[:, None])):
+                lst.append(v)
+    return tuple(torch.cat(v) for v in out)
+
+
+def orbit_camera_rays(n_views, img_wh=(64, 64), radius=1.3, focal_ratio=1.0, seed=23, elevation=(0.15, 0.75)):
+    """Pinhole cameras on a sphere of `radius` around the origin, looking at it: -> (rays_o, rays_d) float32 numpy [n_views * W * H, 3],
+    view-major, directions normalised; focal = focal_ratio * W (1.0: every camera sees the whole [-0.5, 0.5]^3 box)."""
+    rng = np.random.default_rng(seed)
+    phi = 2 * np.pi * (np.arange(n_views) + rng.random()) / n_views
+    z = elevation[0] + (elevation[1] - elevation[0]) * rng.random(n_views)
+    rxy = np.sqrt(1 - z * z)
+    cams = radius * np.stack([rxy * np.cos(phi), rxy * np.sin(phi), z], -1)
+    rot = _look_at(cams.copy(), np.zeros_like(cams), np.zeros(n_views))
+    W, H = img_wh
+    px, py = np.meshgrid(np.arange(W) + 0.5, np.arange(H) + 0.5)
+    d_cam = np.stack([(px - W / 2) / (focal_ratio * W), (py - H / 2) / (focal_ratio * W), np.ones_like(px)], -1).reshape(-1, 3)
+    rays_d = np.einsum('vij,pj->vpi', rot, d_cam)
+    rays_d /= np.linalg.norm(rays_d, axis=-1, keepdims=True)
+    rays_o = np.broadcast_to(cams[:, None, :], rays_d.shape)
+    return rays_o.reshape(-1, 3).astype(np.float32), rays_d.reshape(-1, 3).astype(np.float32)
