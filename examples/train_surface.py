@@ -52,6 +52,8 @@ def main(argv=None):
     ap.add_argument("--warmup_steps", type=int, default=256)
     ap.add_argument("--mesh_res", type=int, default=128)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--n_importance", type=int, default=0,
+                    help="inverse-CDF draws per ray that refine the marched samples (hierarchical sampling); 0: the march alone")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs the GPU: libngp_hip has no CPU path")
@@ -86,7 +88,8 @@ def main(argv=None):
         # a random grey background per step, in the render and in the target alike: over a fixed white one a white sheet in empty
         # space costs nothing, and the opacity of the field is only as right as the colours let it be
         bg = float(torch.rand((), device=dev, generator=gen))
-        res = render_surface(model, o_tr[idx], d_tr[idx], cos_anneal=min(1.0, step / anneal_steps), bg=bg)
+        res = render_surface(model, o_tr[idx], d_tr[idx], cos_anneal=min(1.0, step / anneal_steps), bg=bg,
+                             n_importance=args.n_importance)
         target = torch.where(hit_tr[idx][:, None], rgb_tr[idx], torch.full_like(rgb_tr[idx], bg))
         mse = torch.nn.functional.mse_loss(res["rgb"], target)
         gn = res["grad_norm"]
@@ -105,11 +108,11 @@ def main(argv=None):
     k = min(5, len(losses))
 
     with torch.no_grad():
-        out = render_surface(model, o_te, d_te, test_time=True)
+        out = render_surface(model, o_te, d_te, test_time=True, n_importance=args.n_importance)
         mse_te = float(torch.nn.functional.mse_loss(out["rgb"], rgb_te))
     topo, sdf_err = _mesh_report(model, args.mesh_res, dev)
     info = {"steps": args.steps, "views": args.views, "image": args.wh, "rays_per_step": args.batch, "levels": args.levels, "log2_T": args.log2_T,
-            "max_res": args.max_res, "eikonal_weight": args.eikonal_weight,
+            "max_res": args.max_res, "eikonal_weight": args.eikonal_weight, "n_importance": args.n_importance,
             "loss_first": sum(losses[:k]) / k, "loss_last": sum(losses[-k:]) / k,
             "psnr_heldout": -10.0 * math.log10(max(mse_te, 1e-12)), "inv_s_first": inv_s_first, "inv_s_last": float(model.inv_s().detach()),
             "eikonal_error": float(eik_err), "step_ms": step_ms,

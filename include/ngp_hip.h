@@ -748,6 +748,44 @@ int ngp_surface_composite_bwd(const float* dL_dopacity, const float* dL_ddepth, 
                               float bg, const int32_t* total_samples, const float* alphas, float* d_sdf, float* d_cos, float* d_rgbs,
                               float* d_aux /* may be NULL */, float* d_inv_s /* [1] */, float* workspace /* [n_rays] */, void* stream);
 
+/* ---- importance resampling along rays: inverse-CDF refinement of marched sections (csrc/resample.hip) ---------------------------------
+ * Sample j of a ray is the midpoint t_j of the SECTION [lo_j, hi_j] = [t_j - 0.5f delta_j, t_j + 0.5f delta_j]; gaps between sections
+ * are skipped empty space.  Refinement only cuts sections: the union of a ray's sections stays what it was.  Row i of rays_a is
+ * (ray index, start, N); rays_o, rays_d [n_orig, 3] and noise [n_orig] (in [0, 1)) are indexed by the RAY INDEX, ws, deltas, ts
+ * [n_samples] by start + j.  K >= 1 draws per ray, floor_w >= 0 is added to every weight.  All arithmetic is f32, one rounding per
+ * operation as written (no contraction), per ray in rays_a row order:
+ *     w_j    = (ws_j < 0 ? 0 : ws_j) + floor_w
+ *     c_j    = sum_{i <= j} w_i, summed 64 sections at a time: c_j = carry + (inclusive Kogge-Stone scan of the group, lane j mod 64:
+ *              for d = 1, 2, .., 32: v_l += v_{l-d} for l >= d), carry = the c of the group's last lane, 0 for the first group
+ *     the ray is COPIED THROUGH (every section kept as it is, t and delta bit for bit) if N = 0, if any ws_j is not finite, or if
+ *     c_last = c_{N-1} is not > 0 or not finite
+ *     draw k = 0 .. K-1:  u = (float(k) + noise) / float(K);  target = u c_last
+ *         j      = the first section with c_j > target, by bisection (lo = 0, hi = N; mid = (lo + hi) / 2; c_mid > target ? hi = mid :
+ *                  lo = mid + 1); no such section: the draw is dropped
+ *         t*     = lo_j + (target - c_{j-1}) / w_j * delta_j           (c_{-1} = 0; left to right)
+ *         kept   iff lo_j < t* < hi_j and (k = 0 or t* != the t* of draw k - 1)     (a zero-weight section gives inf / NaN: not kept)
+ *     a section with m >= 1 kept cuts becomes m + 1 children with the edges lo_j, cuts.., hi_j; a child with the edges (a, b) has
+ *     t = 0.5f (a + b), delta = b - a.  A section no cut fell into is its own only child, t_j and delta_j copied bit for bit.  Every
+ *     child has xyz = o + t d per component, dir = d and parent = start + j, the index of its section in the INPUT buffers.
+ *     Children are stored in ascending t: the first child of section j at j + (kept cuts in sections < j), the child that starts at the
+ *     ray's kept cut number r (0-based, in draw order) in section j at j + r + 1.
+ * count : fills the staged cuts stage_t / stage_j [n_rays K] (row i: its kept cuts, compacted, in draw order) and counts[i] = N_i +
+ *         kept_i.  cdf [n_samples] is a workspace: a ray of more than 1024 sections keeps its CDF there, at start + j (shorter rays keep
+ *         it in LDS and leave the workspace untouched).  A row of rays_a that points outside the buffers (ray index outside [0, n_orig), start or N < 0,
+ *         start + N > n_samples) is given the count 0 and sets total[1] = 1; the caller zeroes total[2] beforehand.
+ * scan  : rays_a_out[i] = (ray index of row i, exclusive prefix sum of counts, counts[i]), total[0] = the sum.  One block, no atomics.
+ * write : after count and scan, with the same inputs: xyzs, dirs [total, 3], deltas_out, ts_out, parent [total].
+ * No atomics anywhere: the same inputs give the same bytes.  n_rays <= 0 returns 0 without a launch; -1 for a null required pointer,
+ * K < 1, n_orig < 1, n_samples < 0 or a floor_w that is not >= 0.  The caller keeps n_samples + n_rays K below 2^31. */
+int ngp_resample_count(const float* ws, const float* deltas, const float* ts, const int32_t* rays_a, const float* noise, int n_rays,
+                       int n_orig, long long n_samples, int K, float floor_w, float* cdf, float* stage_t, int32_t* stage_j,
+                       int32_t* counts, int32_t* total /* [2], zeroed */, void* stream);
+int ngp_resample_scan(const int32_t* counts, const int32_t* rays_a, int n_rays, int32_t* rays_a_out, int32_t* total, void* stream);
+int ngp_resample_write(const float* rays_o, const float* rays_d, const float* deltas, const float* ts, const int32_t* rays_a,
+                       const int32_t* rays_a_out, const float* stage_t, const int32_t* stage_j, int n_rays, int n_orig,
+                       long long n_samples, int K, float* xyzs, float* dirs, float* deltas_out, float* ts_out, int32_t* parent,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -922,6 +922,55 @@ def surface_composite_bwd(dL_dopacity, dL_ddepth, dL_drgb, dL_daux, dL_dws, sdf,
     return d_sdf, d_cos, d_rgbs, d_aux, d_inv_s
 
 
+# ---------------------------------------------------------------------------------------------------- importance resampling
+def resample_rays(ws, deltas, ts, rays_a, rays_o, rays_d, noise, K, floor=0.0):
+    """ngp_resample_count -> _scan -> (one D2H read of the total, like march_train) -> _write (csrc/resample.hip; contract in
+    include/ngp_hip.h): K stratified inverse-CDF draws per ray cut the marched sections where the weight ws is.
+    ws, deltas, ts [S]; rays_a [n,3] i32 (ray index, start, count); rays_o, rays_d [n_orig,3] and noise [n_orig] in [0, 1), indexed
+    by the ray index.  -> (rays_a' [n,3], xyzs [S',3], dirs [S',3], deltas [S'], ts [S'], parent [S'] i32, total): the same rows and
+    ray indices, children in ascending t, parent = the index of the coarse sample a child was cut from.  Nothing is differentiable."""
+    for name, t in (("ws", ws), ("deltas", deltas), ("ts", ts), ("rays_o", rays_o), ("rays_d", rays_d), ("noise", noise)):
+        _dev(t, torch.float32, name)
+    _dev(rays_a, torch.int32, "rays_a")
+    S, K = ws.numel(), int(K)
+    if ws.dim() != 1 or deltas.shape != ws.shape or ts.shape != ws.shape:
+        raise ValueError("ws, deltas, ts must be [S]; got %s %s %s" % (tuple(ws.shape), tuple(deltas.shape), tuple(ts.shape)))
+    if rays_a.dim() != 2 or rays_a.shape[1] != 3:
+        raise ValueError("rays_a must be [n_rays, 3], got %s" % (tuple(rays_a.shape),))
+    n, n_orig = rays_a.shape[0], rays_o.shape[0]
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape or tuple(noise.shape) != (n_orig,):
+        raise ValueError("rays_o, rays_d must be [n_orig, 3] and noise [n_orig]; got %s %s %s"
+                         % (tuple(rays_o.shape), tuple(rays_d.shape), tuple(noise.shape)))
+    if K < 1:
+        raise ValueError("K must be at least 1, got %d" % K)
+    if not float(floor) >= 0.0:
+        raise ValueError("floor must be >= 0, got %r" % (floor,))
+    if S + n * K >= 2**31:
+        raise ValueError("S + n_rays K = %d does not fit the int32 sample index" % (S + n * K))
+    dev = ws.device
+    rays_a_out = torch.empty(n, 3, device=dev, dtype=torch.int32)
+    total = torch.zeros(2, device=dev, dtype=torch.int32)
+    empty = lambda m, dt=torch.float32: torch.empty(m, device=dev, dtype=dt)
+    if n == 0:
+        return rays_a_out, empty((0, 3)), empty((0, 3)), empty(0), empty(0), empty(0, torch.int32), total[0]
+    if n_orig < 1:
+        raise ValueError("rays_a has rows but rays_o is empty")
+    L, st = _lib(), _stream()
+    cdf, stage_t, stage_j, counts = empty(S), empty(n * K), empty(n * K, torch.int32), empty(n, torch.int32)
+    check(L.ngp_resample_count(_ptr(ws), _ptr(deltas), _ptr(ts), _ptr(rays_a), _ptr(noise), n, n_orig, S, K, float(floor), _ptr(cdf),
+                               _ptr(stage_t), _ptr(stage_j), _ptr(counts), _ptr(total), st), "ngp_resample_count")
+    check(L.ngp_resample_scan(_ptr(counts), _ptr(rays_a), n, _ptr(rays_a_out), _ptr(total), st), "ngp_resample_scan")
+    S_out, bad = (int(v) for v in total.tolist())
+    if bad:
+        raise ValueError("rays_a has a row outside the buffers (ray index outside [0, %d), or start / count outside [0, %d])" % (n_orig, S))
+    xyzs, dirs, deltas_out, ts_out, parent = empty((S_out, 3)), empty((S_out, 3)), empty(S_out), empty(S_out), empty(S_out, torch.int32)
+    if S_out > 0:
+        check(L.ngp_resample_write(_ptr(rays_o), _ptr(rays_d), _ptr(deltas), _ptr(ts), _ptr(rays_a), _ptr(rays_a_out), _ptr(stage_t),
+                                   _ptr(stage_j), n, n_orig, S, K, _ptr(xyzs), _ptr(dirs), _ptr(deltas_out), _ptr(ts_out), _ptr(parent),
+                                   st), "ngp_resample_write")
+    return rays_a_out, xyzs, dirs, deltas_out, ts_out, parent, total[0]
+
+
 def levels_to_numpy(lv):
     """(scale, resolution, map_size, offset) as numpy arrays -- for tests and for the module buffers."""
     L = lv.n_levels

@@ -3,7 +3,8 @@
 `SurfaceRenderer` / `surface_render_func`  the autograd node over ngp_surface_composite_fwd / _bwd
 `SDFField`                                 hash encoder (twice differentiable) + a small geometry MLP -> (sdf, feature), a colour MLP on
                                            (feature, normal, SH16(dir)), one learnable sharpness, and the occupancy grid the march reads
-`render_surface`                           slab test -> march -> sdf and its gradient -> colours -> compositor -> result dictionary
+`render_surface`                           slab test -> march -> (n_importance > 0: a coarse pass and ops.resample_rays, csrc/resample.hip)
+                                           -> sdf and its gradient -> colours -> compositor -> result dictionary
 
 The opacity of a sample comes from the signed distance f, the directional derivative dir . grad f and the global inverse standard
 deviation s = exp(log_inv_s) (contract: include/ngp_hip.h).  grad f is taken by autograd through the hash encoder's position gradient;
@@ -173,10 +174,35 @@ class SDFField(nn.Module):
         packbits(self.density_grid.reshape(-1).contiguous(), min(mean_density, density_threshold), self.density_bitfield)
 
 
-def _render_chunk(model, rays_o, rays_d, noise, grad, cos_anneal, T_threshold, max_samples, bg):
+def _refine(model, rays_o, rays_d, noise, rays_a, xyzs, dirs, deltas, ts, n_importance, importance_inv_s, cos_anneal, T_threshold):
+    """The coarse pass of hierarchical sampling: f and dir . grad f on the marched samples (no graph; grad mode is on for grad f alone),
+    the compositor's ws at importance_inv_s (None: the model's own sharpness), then n_importance inverse-CDF draws per ray with the
+    ray's march jitter.  The refined positions are detached, as in NeRF and NeuS."""
+    with torch.no_grad():
+        f, _, g = model.sdf_and_grad(xyzs, create_graph=False)
+        cosv = (dirs * g).sum(1)
+        if importance_inv_s is None:
+            inv_s = model.inv_s().detach()
+        else:
+            inv_s = torch.full((1,), float(importance_inv_s), device=xyzs.device)
+        ws = _ops.surface_composite_fwd(f.contiguous(), cosv.contiguous(), torch.zeros_like(xyzs), deltas, ts, rays_a, inv_s.contiguous(),
+                                        cos_anneal, T_threshold)[6]
+        return _ops.resample_rays(ws, deltas, ts, rays_a, rays_o, rays_d, noise, n_importance)
+
+
+def _render_chunk(model, rays_o, rays_d, noise, grad, cos_anneal, T_threshold, max_samples, bg, n_importance=0, importance_inv_s=None):
     hits_t = _ops.ray_aabb(rays_o, rays_d, model.scale)
     rays_a, xyzs, dirs, deltas, ts, total = _ops.march_train(rays_o, rays_d, hits_t, model.density_bitfield, noise, model.cascades,
                                                              model.scale, 0.0, model.grid_size, max_samples)
+    extra = {}
+    if n_importance > 0:
+        extra['rm_samples_coarse'] = total
+        if xyzs.shape[0]:
+            rays_a, xyzs, dirs, deltas, ts, parent, total = _refine(model, rays_o, rays_d, noise, rays_a, xyzs, dirs, deltas, ts,
+                                                                    n_importance, importance_inv_s, cos_anneal, T_threshold)
+        else:
+            parent = torch.zeros(0, device=rays_o.device, dtype=torch.int32)
+        extra['parent'] = parent
     if xyzs.shape[0] == 0:                                     # nothing marched: every ray shows the background
         z = torch.zeros(0, device=rays_o.device)
         f, feat, g = z, torch.zeros(0, model.geo_layers[-1].out_features - 1, device=rays_o.device), torch.zeros(0, 3, device=rays_o.device)
@@ -196,15 +222,21 @@ def _render_chunk(model, rays_o, rays_d, noise, grad, cos_anneal, T_threshold, m
             f.contiguous(), cosv.contiguous(), rgbs.contiguous().float(), deltas, ts, rays_a, inv_s.contiguous(), cos_anneal,
             T_threshold, normal.contiguous(), bg)
         vr = tot.sum()
-    return {'rgb': rgb, 'opacity': opacity, 'depth': depth, 'normal': aux_out, 'ws': ws, 'alphas': alphas, 'rays_a': rays_a,
-            'grad_norm': grad_norm, 'deltas': deltas, 'ts': ts, 'rm_samples': total, 'vr_samples': vr}
+    return dict({'rgb': rgb, 'opacity': opacity, 'depth': depth, 'normal': aux_out, 'ws': ws, 'alphas': alphas, 'rays_a': rays_a,
+                 'grad_norm': grad_norm, 'deltas': deltas, 'ts': ts, 'rm_samples': total, 'vr_samples': vr}, **extra)
 
 
 def render_surface(model, rays_o, rays_d, test_time=False, cos_anneal=1.0, T_threshold=1e-4, max_samples=MAX_SAMPLES, bg=1.0,
-                   chunk=16384):
+                   chunk=16384, n_importance=0, importance_inv_s=None):
     """rays_o, rays_d: [N,3] (directions are normalised here: t, depth and the SDF share one unit).  -> dict rgb [N,3] (blended over
     bg), opacity, depth [N], normal [N,3] (the composited unit normals), ws, alphas, grad_norm [S] (|grad f| per sample, for the eikonal
     term), rays_a, deltas, ts, rm_samples, vr_samples.
+
+    n_importance > 0: hierarchical sampling.  A first pass without a graph takes the compositor's weights on the marched samples at
+    importance_inv_s (None: the model's own sharpness) and cuts the marched sections with n_importance inverse-CDF draws per ray
+    (ops.resample_rays, the ray's march jitter as the draw's); everything above is then rendered on the refined samples.  The dict
+    gains parent [S] i32 (the marched sample each refined one was cut from) and rm_samples_coarse (the march's count).  With
+    n_importance = 0 nothing of this is launched.
 
     Training (test_time=False): jittered march, everything differentiable (the model must be in grad mode).  test_time=True: zero
     jitter, `chunk` rays at a time, no graph -- usable inside torch.no_grad(); grad mode is switched on internally for grad f only.
@@ -215,19 +247,22 @@ def render_surface(model, rays_o, rays_d, test_time=False, cos_anneal=1.0, T_thr
     n = rays_o.shape[0]
     if not test_time:
         noise = torch.rand(n, device=rays_o.device)
-        return _render_chunk(model, rays_o, rays_d, noise, True, cos_anneal, T_threshold, max_samples, bg)
+        return _render_chunk(model, rays_o, rays_d, noise, True, cos_anneal, T_threshold, max_samples, bg, n_importance, importance_inv_s)
     out = None
     per_ray = {k: [] for k in ('rgb', 'opacity', 'depth', 'normal')}
-    rm, vr = 0, 0
+    rm, vr, rm_coarse = 0, 0, 0
     with torch.no_grad():
         for a in range(0, n, chunk):
             b = min(a + chunk, n)
             out = _render_chunk(model, rays_o[a:b].contiguous(), rays_d[a:b].contiguous(), torch.zeros(b - a, device=rays_o.device), False,
-                                cos_anneal, T_threshold, max_samples, bg)
+                                cos_anneal, T_threshold, max_samples, bg, n_importance, importance_inv_s)
             for k in per_ray:
                 per_ray[k].append(out[k])
             rm, vr = rm + out['rm_samples'], vr + out['vr_samples']
+            rm_coarse = rm_coarse + out.get('rm_samples_coarse', 0)
     if out is None:
         raise ValueError("render_surface needs at least one ray")
     out.update({k: torch.cat(v) for k, v in per_ray.items()}, rm_samples=rm, vr_samples=vr)
+    if n_importance > 0:
+        out['rm_samples_coarse'] = rm_coarse
     return out
