@@ -11,7 +11,10 @@ under a cosine anneal that goes 0 -> 1 over the first --anneal_steps steps and o
 warm-up, like NGP).  Then held-out views are rendered, the level set f = 0 is extracted with marching tetrahedra, and one JSON line
 reports: held-out PSNR, inv_s first / last, the mean eikonal error, the mesh's vertex / face counts, Euler characteristic and boundary
 edges, and the mean |true SDF| at the mesh vertices -- for the trained model and for the untrained one (the initial sphere).
-loss_first / loss_last are means over the first / last five steps."""
+loss_first / loss_last are means over the first / last five steps.
+
+--trace: the held-out views are also rendered by sphere tracing (ngp_hip.surface.render_surface_traced, csrc/sdf_trace.hip) and the line
+gains, for both renderers, the held-out PSNR and the milliseconds per frame, and the tracer's mean / max evaluations per ray."""
 import argparse
 import json
 import math
@@ -36,7 +39,21 @@ def _mesh_report(model, res, dev):
     return topo, err
 
 
-def main(argv=None):
+def _frame_ms(render, frames, rounds=3):
+    """milliseconds per frame of render(i) over `frames` frames, the best of `rounds` passes after a warm one"""
+    best = float("inf")
+    for r in range(rounds + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(frames):
+            render(i)
+        torch.cuda.synchronize()
+        if r:
+            best = min(best, 1e3 * (time.perf_counter() - t0) / frames)
+    return best
+
+
+def main(argv=None, return_model=False):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--views", type=int, default=24)
@@ -54,6 +71,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--n_importance", type=int, default=0,
                     help="inverse-CDF draws per ray that refine the marched samples (hierarchical sampling); 0: the march alone")
+    ap.add_argument("--trace", action="store_true",
+                    help="also render the held-out views by sphere tracing; report PSNR and ms per frame of both renderers")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs the GPU: libngp_hip has no CPU path")
@@ -119,8 +138,21 @@ def main(argv=None):
             "mesh_resolution": args.mesh_res, "mesh_vertices": topo["vertices"], "mesh_faces": topo["faces"], "mesh_euler": topo["euler"],
             "mesh_boundary_edges": topo["boundary_edges"], "mesh_sdf_error": sdf_err,
             "untrained_mesh_vertices": topo0["vertices"], "untrained_mesh_sdf_error": sdf_err0}
+    if args.trace:
+        from ngp_hip.surface import render_surface_traced
+        px = args.wh * args.wh
+        view = lambda a, i: a[i * px:(i + 1) * px]
+        with torch.no_grad():
+            tr = render_surface_traced(model, o_te, d_te)
+            mse_tr = float(torch.nn.functional.mse_loss(tr["rgb"], rgb_te))
+            ms_march = _frame_ms(lambda i: render_surface(model, view(o_te, i), view(d_te, i), test_time=True, n_importance=args.n_importance),
+                                 args.test_views)
+            ms_trace = _frame_ms(lambda i: render_surface_traced(model, view(o_te, i), view(d_te, i)), args.test_views)
+        info.update({"psnr_heldout_traced": -10.0 * math.log10(max(mse_tr, 1e-12)), "frame_ms_marched": ms_march, "frame_ms_traced": ms_trace,
+                     "trace_n_eval_mean": float(tr["n_eval"].float().mean()), "trace_n_eval_max": int(tr["n_eval"].max()),
+                     "trace_status_counts": [int((tr["status"] == k).sum()) for k in range(4)]})
     print(json.dumps(info))
-    return info
+    return (info, model) if return_model else info
 
 
 if __name__ == "__main__":

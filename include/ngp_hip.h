@@ -786,6 +786,47 @@ int ngp_resample_write(const float* rays_o, const float* rays_d, const float* de
                        long long n_samples, int K, float* xyzs, float* dirs, float* deltas_out, float* ts_out, int32_t* parent,
                        void* stream);
 
+/* ---- sphere tracing: the geometry value of an SDF field and a ray tracer over it (csrc/sdf_trace.hip) ---------------------------------
+ * THE FIELD.  f(x) for a world position x in the box [-scale, scale]^3, all arithmetic f32:
+ *     x01 = (x - lo) / (hi - lo), lo = -scale, hi = scale (two operations per component);
+ *     enc = the F = 2 hash-grid embedding of x01 over the level table (1..16 levels, dense and hashed), bit for bit what ngp_hash_fwd_f32
+ *           gives on x01 -- on faces and outside the box too; every index stays inside its level;
+ *     h = [x (3) | enc (2 L)];  `depth` times  h <- softplus(W h + b)  with `width` outputs;  f = w_out . h + b_out.
+ *     Every sum starts at its bias and adds its terms in input-index order, one fmaf each.  softplus is torch's Softplus(beta = 100):
+ *     z = 100 h; z > 20 ? h : log1pf(expf(z)) / 100.
+ * wpack, fp32: W0[width][3 + 2 L] | b0[width] | (Wi[width][width] | bi[width]) x (depth - 1) | w_out[width] | b_out.  Supported: width 16,
+ * 32 or 64, depth 1 or 2 (the default field: L = 16, width 64, depth 2).
+ * THE TRACE, per ray, directions unit vectors, dt_min = sqrt(3) / 1024, one rounding per operation as written:
+ *     (t1, t2) = the slab test of the box (near plane 0.01).  A miss on the slab, or a t2 that is not finite: MISS with t = -1.
+ *     t = t1, have_prev = false, n_eval = 0, f_last = 0.  Repeat:
+ *       1. !(t < t2): MISS with t = t2.
+ *       2. the occupancy cell of o + t d (the march's cell rule at step dt_min; cascades == 1: cascade 0 for every point).
+ *       3. cell empty: t' = (the march's skip target from t) + dt_min, have_prev = false; !(t' > t): ABANDONED at t; t = t'.  The
+ *          + dt_min puts the next probe INSIDE the next cell, never on its face.  No evaluation.
+ *       4. cell occupied: n_eval == max_evals: ABANDONED at t.  f = f(o + t d), n_eval += 1, f_last = f; f not finite: ABANDONED at t.
+ *       5. f > eps: prev = (t, f), have_prev = true, t = t + fmaxf(f * step_scale, min_step); repeat.
+ *       6. f >= 0: HIT at t.
+ *       7. !have_prev: INSIDE at t (the surface is in front of the first evaluated point of this occupied stretch).
+ *       8. a = prev, b = (t, f): exactly n_refine bisections, each one evaluation that counts in n_eval and ignores max_evals:
+ *          tm = 0.5f (ta + tb); fm not finite: ABANDONED at tm; fm >= 0 replaces a, otherwise b.
+ *          Then t = ta + ((tb - ta) * fa) / (fa - fb): HIT at t, or ABANDONED at tb if that t is not finite.
+ *     Outputs per ray: status (0 MISS, 1 HIT, 2 INSIDE, 3 ABANDONED), t, xyz = o + t d per component, n_eval, f_last (the last
+ *     evaluated value).  An output depends on its ray alone: no atomics on results, the same bytes whatever the batch order.  Rows
+ *     beyond n_rays are not touched.  stats (may be NULL; two counters the caller zeroes): += the lane slots of the evaluation rounds,
+ *     += the slots that held an evaluation -- a measurement, the only atomics of the launch.
+ * density_bitfield: cascades * grid_size^3 bits in the march's layout; coarse (may be NULL): ngp_bitfield_coarsen of it.
+ * Both return 0 without a launch for n = 0, and -1 -- nothing launched, nothing written -- for n < 0, a null required pointer, a
+ * level table with n_features != 2, no level or more than 16, or a level outside the table, an unsupported width / depth, a table
+ * (or enc_out) that is not 8-byte aligned, scale not > 0, cascades outside 1..8, a grid_size that is not a power of two >= 8 or
+ * whose cascades * grid_size^3 / 512 coarse bits exceed 32 768, eps < 0, step_scale <= 0, min_step < 0, n_refine outside 0..64 or
+ * max_evals outside 0..2^20. */
+int ngp_sdf_eval(const float* xyzs, const float* table, const ngp_hash_levels* lv, const float* wpack, int width, int depth, float scale,
+                 int n, float* f, float* enc_out /* [n, 2 L], may be NULL */, void* stream);
+int ngp_sdf_trace(const float* rays_o, const float* rays_d, const uint8_t* density_bitfield, const uint32_t* coarse /* may be NULL */,
+                  const float* table, const ngp_hash_levels* lv, const float* wpack, int width, int depth, int cascades, float scale,
+                  int grid_size, int n_rays, float eps, float step_scale, float min_step, int n_refine, int max_evals, int32_t* status,
+                  float* t, float* xyz, int32_t* n_eval, float* f_last, unsigned long long* stats /* [2], may be NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

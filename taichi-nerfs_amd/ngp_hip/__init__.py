@@ -1,5 +1,5 @@
 """MI355X-native Instant-NGP hot path: ctypes binding (lib), tensor launchers (ops), SDF surface rendering (surface)."""
 from . import lib, ops  # noqa: F401
 from . import surface  # noqa: F401
-from .ops import resample_rays  # noqa: F401
-from .surface import SDFField, SurfaceRenderer, render_surface, surface_render_func  # noqa: F401
+from .ops import resample_rays, sdf_eval, sdf_pack, sdf_trace  # noqa: F401
+from .surface import SDFField, SurfaceRenderer, render_surface, render_surface_traced, surface_render_func, trace_surface  # noqa: F401

@@ -17,7 +17,7 @@ INCLUDE = os.path.join(os.path.dirname(PKG_ROOT), "include")
 LIB_PATH = os.path.join(CSRC, "libngp_hip.so")
 SOURCES = ["march.hip", "hash_grid.hip", "hash_bwd_lds.hip", "composite.hip", "sh_grid.hip", "mlp.hip", "optim.hip", "distortion.hip", "occupancy.hip", "rays.hip",
            "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip", "hash_grad_input.hip", "hash_grad_input2.hip", "mesh.hip",
-           "ray_grad.hip", "surface.hip", "resample.hip"]
+           "ray_grad.hip", "surface.hip", "resample.hip", "sdf_trace.hip"]
 HEADERS = ["ngp_device.h", "hash_common.h", "hash_lanes.h", "march_common.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 FLAGS_STAMP = LIB_PATH + ".flags"      # the flags the in-tree .so was built with: a flag change rebuilds
@@ -282,6 +282,8 @@ SIGNATURES = {
     "ngp_resample_count": [_P] * 5 + [_I, _I, ctypes.c_longlong, _I, _F] + [_P] * 6,
     "ngp_resample_scan": [_P, _P, _I, _P, _P, _P],
     "ngp_resample_write": [_P] * 8 + [_I, _I, ctypes.c_longlong, _I] + [_P] * 6,
+    "ngp_sdf_eval": [_P, _P, _LV, _P, _I, _I, _F, _I, _P, _P, _P],
+    "ngp_sdf_trace": [_P, _P, _P, _P, _P, _LV, _P, _I, _I, _I, _F, _I, _I, _F, _F, _F, _I, _I] + [_P] * 7,
 }
 
 # declared in include/ngp_hip_experimental.h: exported and typed like the rest, called by no default path of the package

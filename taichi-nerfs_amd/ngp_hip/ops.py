@@ -971,6 +971,95 @@ def resample_rays(ws, deltas, ts, rays_a, rays_o, rays_d, noise, K, floor=0.0):
     return rays_a_out, xyzs, dirs, deltas_out, ts_out, parent, total[0]
 
 
+# ---------------------------------------------------------------------------------------------------- sphere tracing
+SDF_DT_MIN = float(np.float32(1.7320508075688772 / 1024))
+SDF_TRACE_DEFAULTS = dict(eps=1e-4, step_scale=1.0, min_step=SDF_DT_MIN, n_refine=8, max_evals=256)
+
+
+def sdf_pack(layers):
+    """The fp32 weight pack of ngp_sdf_eval / ngp_sdf_trace from the geometry MLP's linear layers (objects with .weight [out, in] and
+    .bias [out]): W0 | b0 | (Wi | bi).. | w_out | b_out, of the last layer row 0 only.  A fresh tensor: a copy of the parameters."""
+    layers = list(layers)
+    if len(layers) < 2:
+        raise ValueError("sdf_pack needs at least one hidden layer and the output layer")
+    parts = []
+    for lin in layers[:-1]:
+        parts += [lin.weight.detach().float().reshape(-1), lin.bias.detach().float().reshape(-1)]
+    parts += [layers[-1].weight.detach().float()[0].reshape(-1), layers[-1].bias.detach().float()[:1]]
+    return torch.cat(parts).contiguous()
+
+
+def sdf_pack_size(n_levels, width, depth):
+    return width * (3 + 2 * n_levels) + width + (depth - 1) * (width * width + width) + width + 1
+
+
+def _sdf_field_check(what, table, lv, wpack, width, depth):
+    width, depth = int(width), int(depth)
+    if lv.n_features != 2 or not 1 <= lv.n_levels <= 16:
+        raise ValueError("%s needs a level table of 1..16 levels with 2 features, got %d x %d" % (what, lv.n_levels, lv.n_features))
+    if width not in (16, 32, 64) or depth not in (1, 2):
+        raise ValueError("%s supports width 16, 32 or 64 and depth 1 or 2, got width %d depth %d" % (what, width, depth))
+    _dev(table, torch.float32, "hash_table"); _dev(wpack, torch.float32, "wpack")
+    if table.numel() != lv.total_entries * 2:
+        raise ValueError("%s: the table must hold %d floats, got %d" % (what, lv.total_entries * 2, table.numel()))
+    if wpack.numel() != sdf_pack_size(lv.n_levels, width, depth):
+        raise ValueError("%s: the pack of %d levels, width %d, depth %d holds %d floats, got %d"
+                         % (what, lv.n_levels, width, depth, sdf_pack_size(lv.n_levels, width, depth), wpack.numel()))
+    return width, depth
+
+
+def sdf_eval(xyzs, table, lv, wpack, width, depth, scale, return_enc=False):
+    """The SDF field's geometry value in one launch (ngp_sdf_eval; contract in include/ngp_hip.h, "sphere tracing"): world positions
+    [n,3] -> f [n], plus the [n, 2 L] embedding with return_enc=True (bit for bit hash_fwd_f32 of the normalised positions)."""
+    _dev(xyzs, torch.float32, "xyzs")
+    n = xyzs.shape[0]
+    if tuple(xyzs.shape) != (n, 3):
+        raise ValueError("sdf_eval: xyzs must be [n, 3], got %s" % (tuple(xyzs.shape),))
+    width, depth = _sdf_field_check("sdf_eval", table, lv, wpack, width, depth)
+    f = torch.empty(n, device=xyzs.device, dtype=torch.float32)
+    enc = torch.empty(n, 2 * lv.n_levels, device=xyzs.device, dtype=torch.float32) if return_enc else None
+    check(_lib().ngp_sdf_eval(_ptr(xyzs), _ptr(table), ctypes.byref(lv), _ptr(wpack), width, depth, float(scale), n, _ptr(f), _ptr(enc),
+                              _stream()), "ngp_sdf_eval")
+    return (f, enc) if return_enc else f
+
+
+def sdf_trace(rays_o, rays_d, density_bitfield, coarse, table, lv, wpack, width, depth, cascades, scale, grid_size, eps=1e-4,
+              step_scale=1.0, min_step=SDF_DT_MIN, n_refine=8, max_evals=256, out=None, stats=None):
+    """Sphere tracing in one launch (ngp_sdf_trace; the rule is the "sphere tracing" block of include/ngp_hip.h).  rays_o, rays_d [n,3]
+    f32, directions unit vectors; density_bitfield uint8 [cascades * grid_size^3 / 8]; coarse: coarse_bitfield(...) or None.
+    -> (status [n] i32: 0 MISS, 1 HIT, 2 INSIDE, 3 ABANDONED; t [n]; xyz [n,3]; n_eval [n] i32; f_last [n]); `out` = that tuple
+    preallocated.  stats: None or a zeroed int64 [2] that receives (lane slots of the evaluation rounds, slots that evaluated)."""
+    f32, i32, n = torch.float32, torch.int32, rays_o.shape[0]
+    cascades, grid_size = int(cascades), int(grid_size)
+    want = [(rays_o, "rays_o", f32, (n, 3)), (rays_d, "rays_d", f32, (n, 3)),
+            (density_bitfield, "density_bitfield", torch.uint8, (cascades * grid_size**3 // 8,))]
+    if coarse is not None:
+        want.append((coarse, "coarse", i32, (cascades * grid_size**3 // 512 // 32,)))
+    if out is not None:
+        status, t, xyz, n_eval, f_last = out
+        want += [(status, "out status", i32, (n,)), (t, "out t", f32, (n,)), (xyz, "out xyz", f32, (n, 3)), (n_eval, "out n_eval", i32, (n,)),
+                 (f_last, "out f_last", f32, (n,))]
+    if stats is not None:
+        want.append((stats, "stats", torch.int64, (2,)))
+    for x, name, dt, shape in want:
+        if x.dtype != dt or tuple(x.shape) != shape:
+            raise ValueError("sdf_trace: %s must be %s %s, got %s %s" % (name, dt, shape, x.dtype, tuple(x.shape)))
+    for x, name, dt, _ in want:
+        _dev(x, dt, name)
+    width, depth = _sdf_field_check("sdf_trace", table, lv, wpack, width, depth)
+    if out is None:
+        dev = rays_o.device
+        out = (torch.empty(n, device=dev, dtype=i32), torch.empty(n, device=dev), torch.empty(n, 3, device=dev),
+               torch.empty(n, device=dev, dtype=i32), torch.empty(n, device=dev))
+    status, t, xyz, n_eval, f_last = out
+    check(_lib().ngp_sdf_trace(_ptr(rays_o), _ptr(rays_d), _ptr(density_bitfield), _ptr(coarse), _ptr(table), ctypes.byref(lv), _ptr(wpack),
+                               width, depth, cascades, float(scale), grid_size, n, float(eps), float(step_scale), float(min_step),
+                               int(n_refine), int(max_evals), _ptr(status), _ptr(t), _ptr(xyz), _ptr(n_eval), _ptr(f_last), _ptr(stats),
+                               _stream()), "ngp_sdf_trace")
+    _touched(*out)
+    return out
+
+
 def levels_to_numpy(lv):
     """(scale, resolution, map_size, offset) as numpy arrays -- for tests and for the module buffers."""
     L = lv.n_levels

@@ -3,6 +3,8 @@
 `SurfaceRenderer` / `surface_render_func`  the autograd node over ngp_surface_composite_fwd / _bwd
 `SDFField`                                 hash encoder (twice differentiable) + a small geometry MLP -> (sdf, feature), a colour MLP on
                                            (feature, normal, SH16(dir)), one learnable sharpness, and the occupancy grid the march reads
+`trace_surface`, `render_surface_traced`   test-time rendering by sphere tracing (csrc/sdf_trace.hip): one launch walks every ray to the zero
+                                           crossing, then sdf_and_grad and color run on that one point per ray
 `render_surface`                           slab test -> march -> (n_importance > 0: a coarse pass and ops.resample_rays, csrc/resample.hip)
                                            -> sdf and its gradient -> colours -> compositor -> result dictionary
 
@@ -146,6 +148,22 @@ class SDFField(nn.Module):
         sh = self.dir_encoder(((dirs + 1) / 2).contiguous()).float()
         return self.rgb_net(torch.cat([feature, normal, sh], 1))
 
+    def packed_geometry(self):
+        """A fresh fp32 pack of the geometry MLP for the sphere tracer (ops.sdf_pack: W0 | b0 | .. | w_out | b_out, of the last layer
+        row 0 alone) from the CURRENT parameters -- a copy: later training steps do not reach it."""
+        return _ops.sdf_pack(self.geo_layers)
+
+    def _trace_arch(self):
+        return self.geo_layers[0].out_features, len(self.geo_layers) - 1
+
+    @torch.no_grad()
+    def sdf_fused(self, x, wpack=None):
+        """sdf(x) through the tracer's field kernel (ops.sdf_eval): one launch, no graph."""
+        width, depth = self._trace_arch()
+        enc = self.pos_encoder
+        return _ops.sdf_eval(x.contiguous().float(), enc.hash_table.detach().contiguous(), enc._levels,
+                             self.packed_geometry() if wpack is None else wpack, width, depth, self.scale)
+
     def density(self, x):
         s = self.inv_s().detach()
         return s * torch.sigmoid(-s * self.sdf(x))
@@ -266,3 +284,50 @@ def render_surface(model, rays_o, rays_d, test_time=False, cos_anneal=1.0, T_thr
     if n_importance > 0:
         out['rm_samples_coarse'] = rm_coarse
     return out
+
+
+@torch.no_grad()
+def trace_surface(model, rays_o, rays_d, wpack=None, coarse=None, out=None, stats=None, **params):
+    """Sphere tracing of an SDFField (ops.sdf_trace; the rule is the "sphere tracing" block of include/ngp_hip.h): rays_o [N,3], rays_d
+    [N,3] UNIT vectors -> dict status [N] i32 (0 MISS, 1 HIT, 2 INSIDE, 3 ABANDONED), t [N], xyz [N,3], n_eval [N] i32, f_last [N].
+    params: eps, step_scale, min_step, n_refine, max_evals.  wpack / coarse: model.packed_geometry() / the coarse occupancy bits, to
+    reuse them over several calls; by default both are made here."""
+    width, depth = model._trace_arch()
+    enc = model.pos_encoder
+    if wpack is None:
+        wpack = model.packed_geometry()
+    if coarse is None:
+        coarse = _ops.coarse_bitfield(model.density_bitfield, model.cascades, model.grid_size)
+    res = _ops.sdf_trace(rays_o, rays_d, model.density_bitfield, coarse, enc.hash_table.detach().contiguous(), enc._levels, wpack, width,
+                         depth, model.cascades, model.scale, model.grid_size, out=out, stats=stats, **params)
+    return dict(zip(("status", "t", "xyz", "n_eval", "f_last"), res))
+
+
+def render_surface_traced(model, rays_o, rays_d, bg=1.0, chunk=1 << 20, **params):
+    """Test-time rendering by sphere tracing: rays_o, rays_d [N,3] (directions are normalised here) -> dict rgb [N,3], opacity, depth [N],
+    normal [N,3], status, n_eval [N] i32.  The trace runs `chunk` rays per launch; sdf_and_grad and color then run on the HIT and
+    INSIDE points only, one per ray: rgb = the shaded colour, opacity 1, depth t, normal grad f / |grad f|.  Every other ray shows
+    bg with opacity, depth and normal 0.  No graph is kept: usable inside torch.no_grad() (grad mode is switched on for grad f alone)."""
+    rays_o = rays_o.contiguous().float()
+    rays_d = rays_d.float()
+    rays_d = (rays_d / torch.linalg.norm(rays_d, dim=1, keepdim=True)).contiguous()
+    n, dev = rays_o.shape[0], rays_o.device
+    if n == 0:
+        raise ValueError("render_surface_traced needs at least one ray")
+    with torch.no_grad():
+        wpack = model.packed_geometry()
+        coarse = _ops.coarse_bitfield(model.density_bitfield, model.cascades, model.grid_size)
+        parts = [trace_surface(model, rays_o[a:a + chunk].contiguous(), rays_d[a:a + chunk].contiguous(), wpack=wpack, coarse=coarse, **params)
+                 for a in range(0, n, chunk)]
+        tr = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+        on = (tr["status"] == 1) | (tr["status"] == 2)
+        rgb = torch.full((n, 3), float(bg), device=dev)
+        normal = torch.zeros(n, 3, device=dev)
+        idx = on.nonzero().squeeze(1)
+        if idx.numel():
+            _, feat, g = model.sdf_and_grad(tr["xyz"][idx].contiguous(), create_graph=False)
+            nrm = g / torch.linalg.norm(g, dim=1).clamp_min(1e-12)[:, None]
+            rgb[idx] = model.color(feat, nrm, rays_d[idx]).float()
+            normal[idx] = nrm
+        return {"rgb": rgb, "opacity": on.float(), "depth": torch.where(on, tr["t"], torch.zeros_like(tr["t"])), "normal": normal,
+                "status": tr["status"], "n_eval": tr["n_eval"]}
