@@ -6,26 +6,18 @@
 // The reference walks each ray serially in one thread and carries transmittance through a global T[] array
 // (with a cross-ray race on T[s+1]).  Here one 64-lane wave owns one ray: 64 consecutive samples are loaded
 // coalesced, transmittance is a wave-level multiplicative scan with a per-ray carry, the per-ray sums are wave
-// reductions, and nothing is shared between rays.  The summation order differs from the serial loop, so these kernels are
-// not bit-checked: every output of every entry is held, element by element, to a float64 model of the serial loop and of
-// its reverse sweep (tests/composite_reference.py) within 4x the error the serial float32 evaluation makes on the same
-// rays; the live count is exact wherever float32 can decide it; samples behind it are exact +0; the fused kernel's
-// forward outputs equal composite_fwd_kernel's bit for bit (tests/test_gpu_composite_exact.py).
+// reductions, and nothing is shared between rays.  The 64-sample group step, the closed-form backward walk, the colour load
+// and the colour-gradient store are defined once in composite_common.h (surface.hip takes the group step from there too):
+// composite_bwd_kernel and pass 2 of the fused kernel are that one backward walk.  The forward walk is written twice, in
+// composite_fwd_kernel and in pass 1 of the fused kernel (why: at composite_fwd_kernel).
+// The summation order differs from the serial loop, so these kernels are not bit-checked: every output of every entry is held, element by element, to a float64 model of the
+// serial loop and of its reverse sweep (tests/composite_reference.py) within 4x the error the serial float32 evaluation
+// makes on the same rays; the live count is exact wherever float32 can decide it; samples behind it are exact +0; the
+// fused kernel's forward outputs equal composite_fwd_kernel's bit for bit (tests/test_gpu_composite_exact.py).
 #include "ngp_device.h"
-#include <hip/hip_fp16.h>
+#include "composite_common.h"
 
 namespace ngp {
-
-template <bool HALF>
-__device__ __forceinline__ void load_rgb(const void* rgbs, size_t s, float c[3]) {
-    if (HALF) {
-        const __half* p = (const __half*)rgbs + 3 * s;
-        c[0] = __half2float(p[0]); c[1] = __half2float(p[1]); c[2] = __half2float(p[2]);
-    } else {
-        const float* p = (const float*)rgbs + 3 * s;
-        c[0] = p[0]; c[1] = p[1]; c[2] = p[2];
-    }
-}
 
 // ---- a-7 forward (volume_train.py:22-48) --------------------------------------------------------------
 template <bool HALF>
@@ -42,6 +34,9 @@ __global__ void __launch_bounds__(256) composite_fwd_kernel(const float* __restr
     float T = 1.0f;                       // transmittance entering the current chunk (wave-uniform)
     float r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f, op = 0.f;
     int cnt = 0;
+    // (this walk is pass 1 of composite_train_fused_kernel, statement for statement.  As one function, and also around group_step,
+    // this kernel compiled to other instructions and twice missed the timing rule, profiles/composite_refactor.md: it keeps the
+    // parent's text.  tests/test_gpu_composite_exact.py holds the two kernels to the same bits.)
     for (int base = 0; base < N; base += NGP_WAVE) {
         const int j = base + lane;
         const bool valid = j < N;
@@ -56,12 +51,11 @@ __global__ void __launch_bounds__(256) composite_fwd_kernel(const float* __restr
             tm = ts[s];
             load_rgb<HALF>(rgbs, s, c);
         }
+        // group_step / group_carry of composite_common.h, spelled out (see above; the prefix-liveness rule is explained there)
         const float incl = wave_scan_mul(1.0f - a, lane);                           // prod_{i<=lane} (1-a_i)
         float excl = __shfl_up(incl, 1, NGP_WAVE);
         if (lane == 0) excl = 1.0f;
         const float Ts = T * excl;                                                   // T before this sample
-        // liveness as a PREFIX by construction: the Kogge-Stone product is not guaranteed monotone to the last ulp, and
-        // ngp_live_compact takes the live samples of a ray to be exactly its first vr[r] ones
         const uint64_t deadm = __ballot(valid && !(Ts > thr));
         const bool live = valid && (deadm == 0 || lane < __builtin_ctzll(deadm));
         const float w = live ? a * Ts : 0.0f;                                        // :40
@@ -83,11 +77,7 @@ __global__ void __launch_bounds__(256) composite_fwd_kernel(const float* __restr
     }
 }
 
-// ---- a-7 backward: closed form ---------------------------------------------------
-//   dL/dc_s     = g_rgb * w_s
-//   dL/dsigma_s = delta_s * [ g_rgb.(c_s T+ - (R - rbar_s)) + g_dep (t_s T+ - (D - dbar_s)) + g_op (1 - O)
-//                             + g_ws[s] T+ - (W - wbar_s) ]
-// with T+ = T_s (1 - a_s), bars = inclusive prefix sums, R/D/O the forward outputs, W = sum_s g_ws[s] w_s.
+// ---- a-7 backward: closed form (composite_backward_walk in composite_common.h) ---------------------------------------------
 template <bool HALF>
 __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restrict__ g_op, const float* __restrict__ g_dep,
                                                             const float* __restrict__ g_rgb, const float* __restrict__ g_ws,
@@ -112,63 +102,25 @@ __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restr
         for (int j = lane; j < N; j += NGP_WAVE) W += g_ws[(size_t)start + j] * ws[(size_t)start + j];
         W = wave_sum(W);
     }
-    float T = 1.0f;
-    float cr0 = 0.f, cr1 = 0.f, cr2 = 0.f, cd = 0.f, cw = 0.f;     // carries of the inclusive prefix sums
-    for (int base = 0; base < N; base += NGP_WAVE) {
-        const int j = base + lane;
-        const bool valid = j < N;
-        const size_t s = (size_t)start + j;
-        if (!(T > thr)) {
-            if (valid) {
-                d_sigmas[s] = 0.0f;
-                if (HALF) { __half* p = (__half*)d_rgbs + 3 * s; p[0] = p[1] = p[2] = __float2half(0.0f); }
-                else { float* p = (float*)d_rgbs + 3 * s; p[0] = p[1] = p[2] = 0.0f; }
-            }
-            continue;
-        }
-        float a = 0.0f, tm = 0.0f, dl = 0.0f, gw = 0.0f, c[3] = {0.f, 0.f, 0.f};
-        if (valid) {
-            dl = deltas[s];
-            a = 1.0f - expf(-sigmas[s] * dl);
-            tm = ts[s];
-            load_rgb<HALF>(rgbs, s, c);
-            if (g_ws) gw = g_ws[s];
-        }
-        const float incl = wave_scan_mul(1.0f - a, lane);
-        float excl = __shfl_up(incl, 1, NGP_WAVE);
-        if (lane == 0) excl = 1.0f;
-        const float Ts = T * excl;
-        // liveness as a PREFIX by construction: the Kogge-Stone product is not guaranteed monotone to the last ulp, and
-        // ngp_live_compact takes the live samples of a ray to be exactly its first vr[r] ones
-        const uint64_t deadm = __ballot(valid && !(Ts > thr));
-        const bool live = valid && (deadm == 0 || lane < __builtin_ctzll(deadm));
-        const float w = live ? a * Ts : 0.0f;
-        const float Tp = Ts * (1.0f - a);
-        const float p0 = cr0 + wave_scan_add(w * c[0], lane);
-        const float p1 = cr1 + wave_scan_add(w * c[1], lane);
-        const float p2 = cr2 + wave_scan_add(w * c[2], lane);
-        const float pd = cd + wave_scan_add(w * tm, lane);
-        float pw = 0.0f;
-        if (g_ws) pw = cw + wave_scan_add(gw * w, lane);
-        if (valid) {
-            float ds = 0.0f, dc0 = 0.0f, dc1 = 0.0f, dc2 = 0.0f;
-            if (live) {
-                float acc = gr0 * (c[0] * Tp - (R0 - p0)) + gr1 * (c[1] * Tp - (R1 - p1)) + gr2 * (c[2] * Tp - (R2 - p2));
-                acc += gd * (tm * Tp - (D - pd));
-                acc += go * (1.0f - O);
-                acc += gw * Tp - (W - pw);
-                ds = dl * acc;
-                dc0 = gr0 * w; dc1 = gr1 * w; dc2 = gr2 * w;
-            }
-            d_sigmas[s] = ds;
-            if (HALF) { __half* p = (__half*)d_rgbs + 3 * s; p[0] = __float2half(dc0); p[1] = __float2half(dc1); p[2] = __float2half(dc2); }
-            else { float* p = (float*)d_rgbs + 3 * s; p[0] = dc0; p[1] = dc1; p[2] = dc2; }
-        }
-        cr0 = __shfl(p0, NGP_WAVE - 1, NGP_WAVE); cr1 = __shfl(p1, NGP_WAVE - 1, NGP_WAVE);
-        cr2 = __shfl(p2, NGP_WAVE - 1, NGP_WAVE); cd = __shfl(pd, NGP_WAVE - 1, NGP_WAVE);
-        if (g_ws) cw = __shfl(pw, NGP_WAVE - 1, NGP_WAVE);
-        T = deadm ? 0.0f : T * __shfl(incl, NGP_WAVE - 1, NGP_WAVE);    // a dead sample in this chunk ends the ray for good
+    composite_backward_walk<HALF, true>(sigmas, rgbs, deltas, ts, g_ws, d_sigmas, d_rgbs, start, N, thr, lane,
+                                        RayCotangents{gr0, gr1, gr2, gd, go}, RayTotals{R0, R1, R2, D, O, W});
+}
+
+// One returning atomic per block claims an output range: on entry s_off[0 .. n_slots) holds the slots' counts (n_slots <= 64), on
+// return the first output index of each.  Every thread of the block calls it (two block barriers); a block with nothing to append
+// issues no atomic.
+__device__ __forceinline__ void block_claim(int* s_off, int n_slots, int32_t* __restrict__ counter) {
+    const int lane = lane_id();
+    __syncthreads();
+    if (threadIdx.x < NGP_WAVE) {                    // wave 0: one count per lane
+        const int c = lane < n_slots ? s_off[lane] : 0;
+        const int inc = wave_scan_add_i(c, lane);
+        int base = 0;
+        if (lane == NGP_WAVE - 1 && inc > 0) base = atomicAdd(counter, inc);
+        base = __shfl(base, NGP_WAVE - 1, NGP_WAVE);
+        if (lane < n_slots) s_off[lane] = base + inc - c;
     }
+    __syncthreads();
 }
 
 // ---- trainer fusion: forward + MSE gradient + backward of one ray in one wave -----------------------------------
@@ -194,7 +146,7 @@ __global__ void __launch_bounds__(LIVE ? 1024 : 256) composite_train_fused_kerne
     const int n = has_ray ? n_raw : 0;
     const int lane = lane_id();
     const int ray_idx = rays_a[3 * n], start = rays_a[3 * n + 1], N = has_ray ? rays_a[3 * n + 2] : 0;
-    // ---- pass 1: forward (same arithmetic as composite_fwd_kernel)
+    // ---- pass 1: forward (composite_fwd_kernel's walk, statement for statement)
     float T = 1.0f, r0 = 0.f, r1 = 0.f, r2 = 0.f, dep = 0.f, op = 0.f;
     int cnt = 0;
     for (int base = 0; base < N; base += NGP_WAVE) {
@@ -204,18 +156,11 @@ __global__ void __launch_bounds__(LIVE ? 1024 : 256) composite_train_fused_kerne
         if (!(T > thr)) { if (valid) ws[s] = 0.0f; continue; }
         float a = 0.0f, tm = 0.0f, c[3] = {0.f, 0.f, 0.f};
         if (valid) { a = 1.0f - expf(-sigmas[s] * deltas[s]); tm = ts[s]; load_rgb<HALF>(rgbs, s, c); }
-        const float incl = wave_scan_mul(1.0f - a, lane);
-        float excl = __shfl_up(incl, 1, NGP_WAVE);
-        if (lane == 0) excl = 1.0f;
-        const float Ts = T * excl;
-        // liveness as a PREFIX by construction: the Kogge-Stone product is not guaranteed monotone to the last ulp, and
-        // ngp_live_compact takes the live samples of a ray to be exactly its first vr[r] ones
-        const uint64_t deadm = __ballot(valid && !(Ts > thr));
-        const bool live = valid && (deadm == 0 || lane < __builtin_ctzll(deadm));
-        const float w = live ? a * Ts : 0.0f;
+        const GroupStep g = group_step(T, a, valid, thr, lane);
+        const float w = g.w;
         if (valid) ws[s] = w;
-        r0 += w * c[0]; r1 += w * c[1]; r2 += w * c[2]; dep += w * tm; op += w; cnt += live ? 1 : 0;
-        T = deadm ? 0.0f : T * __shfl(incl, NGP_WAVE - 1, NGP_WAVE);    // a dead sample in this chunk ends the ray for good
+        r0 += w * c[0]; r1 += w * c[1]; r2 += w * c[2]; dep += w * tm; op += w; cnt += g.live ? 1 : 0;
+        T = group_carry(T, g);
     }
     const float R0 = wave_sum(r0), R1 = wave_sum(r1), R2 = wave_sum(r2), D = wave_sum(dep), O = wave_sum(op);
     cnt = wave_sum_i(cnt);
@@ -232,64 +177,14 @@ __global__ void __launch_bounds__(LIVE ? 1024 : 256) composite_train_fused_kerne
         // 100 us) -- the reader reduces this array instead
         if (sq_err) sq_err[ray_idx] = e0 * e0 + e1 * e1 + e2 * e2;
     }
-    // ---- pass 2: closed-form backward (composite_bwd_kernel with g_depth = g_ws = 0)
-    T = 1.0f;
-    float cr0 = 0.f, cr1 = 0.f, cr2 = 0.f;
-    for (int base = 0; base < N; base += NGP_WAVE) {
-        const int j = base + lane;
-        const bool valid = j < N;
-        const size_t s = (size_t)start + j;
-        if (!(T > thr)) {
-            if (valid) {
-                d_sigmas[s] = 0.0f;
-                if (HALF) { __half* p = (__half*)d_rgbs + 3 * s; p[0] = p[1] = p[2] = __float2half(0.0f); }
-                else { float* p = (float*)d_rgbs + 3 * s; p[0] = p[1] = p[2] = 0.0f; }
-            }
-            continue;
-        }
-        float a = 0.0f, dl = 0.0f, c[3] = {0.f, 0.f, 0.f};
-        if (valid) { dl = deltas[s]; a = 1.0f - expf(-sigmas[s] * dl); load_rgb<HALF>(rgbs, s, c); }
-        const float incl = wave_scan_mul(1.0f - a, lane);
-        float excl = __shfl_up(incl, 1, NGP_WAVE);
-        if (lane == 0) excl = 1.0f;
-        const float Ts = T * excl;
-        // liveness as a PREFIX by construction: the Kogge-Stone product is not guaranteed monotone to the last ulp, and
-        // ngp_live_compact takes the live samples of a ray to be exactly its first vr[r] ones
-        const uint64_t deadm = __ballot(valid && !(Ts > thr));
-        const bool live = valid && (deadm == 0 || lane < __builtin_ctzll(deadm));
-        const float w = live ? a * Ts : 0.0f;
-        const float Tp = Ts * (1.0f - a);
-        const float p0 = cr0 + wave_scan_add(w * c[0], lane), p1 = cr1 + wave_scan_add(w * c[1], lane),
-                    p2 = cr2 + wave_scan_add(w * c[2], lane);
-        if (valid) {
-            float ds = 0.0f, dc0 = 0.0f, dc1 = 0.0f, dc2 = 0.0f;
-            if (live) {
-                float acc = gr0 * (c[0] * Tp - (R0 - p0)) + gr1 * (c[1] * Tp - (R1 - p1)) + gr2 * (c[2] * Tp - (R2 - p2));
-                acc += go * (1.0f - O);
-                ds = dl * acc;
-                dc0 = gr0 * w; dc1 = gr1 * w; dc2 = gr2 * w;
-            }
-            d_sigmas[s] = ds;
-            if (HALF) { __half* p = (__half*)d_rgbs + 3 * s; p[0] = __float2half(dc0); p[1] = __float2half(dc1); p[2] = __float2half(dc2); }
-            else { float* p = (float*)d_rgbs + 3 * s; p[0] = dc0; p[1] = dc1; p[2] = dc2; }
-        }
-        cr0 = __shfl(p0, NGP_WAVE - 1, NGP_WAVE); cr1 = __shfl(p1, NGP_WAVE - 1, NGP_WAVE); cr2 = __shfl(p2, NGP_WAVE - 1, NGP_WAVE);
-        T = deadm ? 0.0f : T * __shfl(incl, NGP_WAVE - 1, NGP_WAVE);    // a dead sample in this chunk ends the ray for good
-    }
+    // ---- pass 2: closed-form backward (composite_bwd_kernel's walk without the depth and g_ws terms)
+    composite_backward_walk<HALF, false>(sigmas, rgbs, deltas, ts, nullptr, d_sigmas, d_rgbs, start, N, thr, lane,
+                                         RayCotangents{gr0, gr1, gr2, 0.0f, go}, RayTotals{R0, R1, R2, D, O, 0.0f});
     if (LIVE) {
         __shared__ int s_off[16];
-        const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+        const int wave = threadIdx.x >> 6;
         if (lane == 0) s_off[wave] = has_ray ? cnt : 0;
-        __syncthreads();
-        if (wave == 0) {
-            const int c = lane < nw ? s_off[lane] : 0;
-            const int inc = wave_scan_add_i(c, lane);
-            int base = 0;
-            if (lane == NGP_WAVE - 1 && inc > 0) base = atomicAdd(live_total, inc);
-            base = __shfl(base, NGP_WAVE - 1, NGP_WAVE);
-            if (lane < nw) s_off[lane] = base + inc - c;
-        }
-        __syncthreads();
+        block_claim(s_off, blockDim.x >> 6, live_total);
         if (has_ray) {
             const int b = s_off[wave];
             for (int k = lane; k < cnt; k += NGP_WAVE) live_idx[b + k] = start + k;
@@ -344,18 +239,9 @@ constexpr int LIST_LANES = 16, LIST_RPB = 1024 / LIST_LANES;
 
 // appends `c` consecutive sample indices first .. first + c of this 16-lane group's ray to list (block-wise range allocation)
 __device__ __forceinline__ void list_append_block(int c, int first, int32_t* __restrict__ list, int32_t* __restrict__ count, int* s_off) {
-    const int grp = threadIdx.x / LIST_LANES, sub = threadIdx.x % LIST_LANES, lane = lane_id();
+    const int grp = threadIdx.x / LIST_LANES, sub = threadIdx.x % LIST_LANES;
     if (sub == 0) s_off[grp] = c;
-    __syncthreads();
-    if (threadIdx.x < NGP_WAVE) {                    // wave 0: LIST_RPB == 64 counts, one per lane
-        const int v = s_off[lane];
-        const int inc = wave_scan_add_i(v, lane);
-        int base = 0;
-        if (lane == NGP_WAVE - 1 && inc > 0) base = atomicAdd(count, inc);
-        base = __shfl(base, NGP_WAVE - 1, NGP_WAVE);
-        s_off[lane] = base + inc - v;
-    }
-    __syncthreads();
+    block_claim(s_off, LIST_RPB, count);             // LIST_RPB == 64 counts, one per lane of wave 0
     const int b = s_off[grp];
     for (int k = sub; k < c; k += LIST_LANES) list[b + k] = first + k;
 }

@@ -239,6 +239,8 @@ __global__ void __launch_bounds__(64 * WAVES) march_fused_kernel(const float* __
     if (sub == 0) s_off[wv * GROUPS + grp] = has_ray ? n : 0;
     __threadfence_block();                                  // the staging rows are read back by other lanes below
     __syncthreads();
+    // (not composite.hip's block_claim: this atomic is unconditional -- the comment at the end rests on it -- and gives an
+    // empty ray the running counter)
     if (wv == 0) {
         const int c = lane < RPB ? s_off[lane] : 0;
         const int inc = wave_scan_add_i(c, lane);

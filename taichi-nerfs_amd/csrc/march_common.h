@@ -1,6 +1,8 @@
-// march_common.h -- the march step rule, the coarse-block table and the slab test, shared by march.hip (the march kernels) and
-// deploy.hip (the fused march-shade-composite of the deployment renderer).  One definition each: a kernel that walks a ray through
-// the occupancy grid includes this header and calls these.
+// march_common.h -- the march step rule, the coarse-block table and the slab test, shared by march.hip (the march kernels),
+// deploy.hip (the fused march-shade-composite of the deployment renderer) and sdf_trace.hip (the sphere tracer's empty-space skip).
+// One definition each: a kernel that walks a ray through the occupancy grid includes this header and calls these.  (The occupancy
+// test of a probed cell is NOT here: as a shared function it changed all three kernels' code and two of them measured slower,
+// profiles/composite_refactor.md; each kernel spells its three lines.)
 #pragma once
 #include "ngp_device.h"
 

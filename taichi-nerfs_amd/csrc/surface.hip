@@ -12,7 +12,9 @@
 // and then the loop of composite.hip unchanged (T = 1; stop at the first !(T > thr); w = a T; ...; T <- T (1 - a)).
 //
 // Shape: one 64-lane wave owns a ray, 64 consecutive samples are loaded coalesced, transmittance is a multiplicative wave scan with a
-// per-ray carry, liveness is a prefix (ballot + ctz), a group is skipped when T <= thr at its start.  The backward is the REVERSE
+// per-ray carry, liveness is a prefix (ballot + ctz), a group is skipped when T <= thr at its start.  That 64-sample group step is
+// composite.hip's own, defined once in composite_common.h: the forward calls group_step, the backward's sweep takes its first half,
+// group_scan.  The forward keeps its own ray walk (another opacity source, the aux accumulators, the alphas store).  The backward is the REVERSE
 // SWEEP of the loop (the adjoint X of the transmittance behind a sample obeys X_{j-1} = G_j a_j + (1 - a_j) X_j), not the closed
 // form `total - prefix` of composite.hip: that form divides by 1 - a_j, and a NeuS opacity is exactly 1 as soon as a ray starts
 // inside the surface.  The sweep runs the 64-sample groups of a ray last to first; inside a group the recurrence is a suffix scan
@@ -25,6 +27,7 @@
 // Held, element by element, to the float64 model of tests/surface_reference.py within 4x the error of a serial float32 evaluation
 // (tests/test_gpu_surface.py).
 #include "ngp_device.h"
+#include "composite_common.h"
 
 namespace ngp {
 
@@ -81,21 +84,14 @@ __global__ void __launch_bounds__(256) surface_fwd_kernel(const float* __restric
             c[0] = rgbs[3 * k]; c[1] = rgbs[3 * k + 1]; c[2] = rgbs[3 * k + 2];
             if (aux) { x[0] = aux[3 * k]; x[1] = aux[3 * k + 1]; x[2] = aux[3 * k + 2]; }
         }
-        const float incl = wave_scan_mul(1.0f - a, lane);                           // prod_{i<=lane} (1-a_i)
-        float excl = __shfl_up(incl, 1, NGP_WAVE);
-        if (lane == 0) excl = 1.0f;
-        const float Ts = T * excl;                                                   // T before this sample
-        // liveness as a PREFIX by construction (the Kogge-Stone product is not monotone to the last ulp): the live samples of a ray
-        // are exactly its first total_samples ones, which is what the backward relies on
-        const uint64_t deadm = __ballot(valid && !(Ts > thr));
-        const bool live = valid && (deadm == 0 || lane < __builtin_ctzll(deadm));
-        const float w = live ? a * Ts : 0.0f;
-        if (valid) { ws[k] = w; alphas[k] = live ? a : 0.0f; }
+        const GroupStep g = group_step(T, a, valid, thr, lane);          // the live samples are a prefix: the backward relies on it
+        const float w = g.w;
+        if (valid) { ws[k] = w; alphas[k] = g.live ? a : 0.0f; }
         r0 += w * c[0]; r1 += w * c[1]; r2 += w * c[2];
         x0 += w * x[0]; x1 += w * x[1]; x2 += w * x[2];
         dep += w * tm; op += w;
-        cnt += live ? 1 : 0;
-        T = deadm ? 0.0f : T * __shfl(incl, NGP_WAVE - 1, NGP_WAVE);    // a dead sample in this group ends the ray for good
+        cnt += g.live ? 1 : 0;
+        T = group_carry(T, g);
     }
     r0 = wave_sum(r0); r1 = wave_sum(r1); r2 = wave_sum(r2);
     dep = wave_sum(dep); op = wave_sum(op); cnt = wave_sum_i(cnt);
@@ -184,10 +180,7 @@ __global__ void __launch_bounds__(256) surface_bwd_kernel(const float* __restric
                 if (g_ws) gw = g_ws[k];
             }
             const float a = al.a, q = 1.0f - a;
-            const float incl = wave_scan_mul(q, lane);
-            float excl = __shfl_up(incl, 1, NGP_WAVE);
-            if (lane == 0) excl = 1.0f;
-            const float Ts = Tg * excl;                                              // T before this sample
+            const float Ts = group_scan(Tg, a, lane).Ts;                             // T before this sample
             // cotangent of w_j
             float G = (gr0 * col[0] + gr1 * col[1]) + gr2 * col[2];
             G += (ga0 * x[0] + ga1 * x[1]) + ga2 * x[2];

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(CSRC, "libngp_hip.so")
 SOURCES = ["march.hip", "hash_grid.hip", "hash_bwd_lds.hip", "composite.hip", "sh_grid.hip", "mlp.hip", "optim.hip", "distortion.hip", "occupancy.hip", "rays.hip",
            "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip", "hash_grad_input.hip", "hash_grad_input2.hip", "mesh.hip",
            "ray_grad.hip", "surface.hip", "resample.hip", "sdf_trace.hip"]
-HEADERS = ["ngp_device.h", "hash_common.h", "hash_lanes.h", "march_common.h"]
+HEADERS = ["ngp_device.h", "hash_common.h", "hash_lanes.h", "march_common.h", "composite_common.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 FLAGS_STAMP = LIB_PATH + ".flags"      # the flags the in-tree .so was built with: a flag change rebuilds
 
