@@ -5,7 +5,7 @@
  * (taichi-dev/taichi-nerfs).  Every entry point replaces ONE Taichi kernel launch of the reference;
  * the reference file:line each one stands in for is cited next to it.  The reference binds its kernels
  * through Taichi's torch zero-copy interop (tensor -> raw device pointer); the binding a maintainer adds
- * instead is the ctypes stub shown in INTEGRATION.md (it is what taichi-nerfs_amd/ngp_hip/lib.py does).
+ * instead is the ctypes stub shown in INTEGRATION.md (taichi-nerfs_amd/ngp_hip/lib.py derives it from this file).
  *
  * Conventions
  *   - plain C: raw DEVICE pointers + explicit sizes; no torch types; no allocation; no host sync
