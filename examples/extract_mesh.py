@@ -99,6 +99,8 @@ def main(argv=None):
     ap.add_argument("--threshold", type=float, default=None, help="density level (default: the occupancy threshold 0.01 * 1024 / sqrt(3))")
     ap.add_argument("--normals", default="grid", choices=["grid", "analytic", "none"])
     ap.add_argument("--out", default="mesh.ply", help=".ply or .obj")
+    ap.add_argument("--compare", default=None, metavar="PATH.ply",
+                    help="also report surface_distance (mean / max, both ways) between the extracted mesh and this one (.ply or .obj)")
     ap.add_argument("--scale", type=float, default=0.5)
     # the --sdf fit (fit_sdf_eikonal.py's options); --max_res also sizes the NGP of --ckpt
     ap.add_argument("--steps", type=int, default=500)
@@ -157,6 +159,12 @@ def main(argv=None):
     info.update(mesh.topology(msh))
     info.update(resolution=args.resolution, normals=args.normals, out=args.out, prepare_seconds=t1 - t0, extract_seconds=t2 - t1,
                 write_seconds=t3 - t2)
+    if args.compare:
+        from ngp_hip import surface_distance
+        other = (mesh.read_ply if args.compare.endswith(".ply") else mesh.read_obj)(args.compare)
+        found = msh.faces.shape[0] > 0 and other.faces.shape[0] > 0           # an empty surface has no distance: null
+        info.update(compare=args.compare,
+                    surface_distance=surface_distance(msh, other, 65536, torch.Generator().manual_seed(args.seed)) if found else None)
     print(json.dumps(info))
     info.update(mesh=msh, grid=grid)
     return info

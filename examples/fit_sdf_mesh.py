@@ -1,0 +1,106 @@
+"""Fit a signed-distance field to a triangle mesh: supervision from geometry instead of from images, and a mesh -> field -> mesh round trip
+that is measured at both ends.  Needs no data file.
+
+    python examples/fit_sdf_mesh.py
+    python examples/fit_sdf_mesh.py --steps 200 --n 4096 --log2_T 14 --levels 8 --max_res 128 --target_resolution 32 --resolution 48
+
+The target is made here: a torus (R 0.25, r 0.1, centred in [-0.5, 0.5]^3), extracted with marching tetrahedra from its analytic SDF at
+--target_resolution cells per axis.  MeshSDF answers the distance to THAT MESH (BVH closest-point query, csrc/mesh_sdf.hip) at the
+points MeshSDF.sample draws every step: most near the surface, the rest uniform in the padded bounding box.  SDFField (hash encoder,
+twice differentiable, + MLP, starting as a sphere of radius 0.25) is fitted with
+    loss = mean |f - sdf_mesh| + eikonal_weight * mean (|grad_x f| - 1)^2
+as in fit_sdf_eikonal.py, and its zero set is extracted again at --resolution.  One JSON line reports the SDF loss first / last, the
+eikonal error, surface_distance between the target and the result (and the untrained sphere) in units of the extraction cell, topology()
+of both meshes and the time of the distance query per step."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "taichi-nerfs_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch  # noqa: E402
+
+BOUNDS = ((-0.5, -0.5, -0.5), (0.5, 0.5, 0.5))
+
+
+def torus_sdf(x, R=0.25, r=0.1):
+    return torch.sqrt((torch.linalg.norm(x[:, :2], dim=1) - R) ** 2 + x[:, 2] ** 2) - r
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--n", type=int, default=16384, help="points per step")
+    ap.add_argument("--log2_T", type=int, default=19)
+    ap.add_argument("--levels", type=int, default=16)
+    ap.add_argument("--max_res", type=int, default=1024)
+    ap.add_argument("--lr", type=float, default=2e-3)
+    ap.add_argument("--eikonal_weight", type=float, default=0.05)
+    ap.add_argument("--sigma", type=float, default=0.02, help="scale of the offset of the near-surface samples")
+    ap.add_argument("--uniform_fraction", type=float, default=0.25)
+    ap.add_argument("--target_resolution", type=int, default=128, help="cells per axis of the target's extraction")
+    ap.add_argument("--resolution", type=int, default=128, help="cells per axis of the result's extraction")
+    ap.add_argument("--compare_n", type=int, default=65536, help="samples per direction of surface_distance")
+    ap.add_argument("--seed", type=int, default=7)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("this example needs the GPU: libngp_hip has no CPU path")
+    dev = torch.device("cuda")
+    torch.manual_seed(args.seed)
+    from ngp_hip import MeshSDF, SDFField, surface_distance
+    from ngp_hip.mesh import extract_mesh, topology
+
+    target = extract_mesh(torus_sdf, args.target_resolution, 0.0, bounds=BOUNDS, sign=-1, normals=None, device=dev)
+    target_sdf = MeshSDF.from_mesh(target)
+    field = SDFField(scale=0.5, levels=args.levels, log2_T=args.log2_T, max_res=args.max_res).to(dev)
+    cell = 1.0 / args.resolution
+
+    def extract():
+        return extract_mesh(field.sdf, args.resolution, 0.0, bounds=BOUNDS, sign=-1, normals=None, device=dev)
+
+    def compare(mesh):
+        if mesh.faces.shape[0] == 0:
+            return None
+        sd = surface_distance(target, mesh, args.compare_n, torch.Generator().manual_seed(args.seed))
+        return {"mean_cells": sd["mean"] / cell, "max_cells": sd["max"] / cell}
+
+    untrained = compare(extract())
+    opt = torch.optim.Adam(field.geo_layers.parameters(), lr=args.lr, eps=1e-15)
+    opt.add_param_group({"params": field.pos_encoder.parameters()})
+    gen = torch.Generator().manual_seed(args.seed)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    hist, query_ms = [], 0.0
+    for step in range(args.steps):
+        x = target_sdf.sample(args.n, args.sigma, args.uniform_fraction, gen).clamp_(-0.5, 0.5)
+        t0.record()
+        d = target_sdf(x, details=False).sdf
+        t1.record()
+        f, _, grad = field.sdf_and_grad(x.requires_grad_(), create_graph=True)
+        norm = torch.linalg.norm(grad, dim=1)
+        sdf_loss = (f - d).abs().mean()
+        loss = sdf_loss + args.eikonal_weight * ((norm - 1.0) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        t1.synchronize()
+        query_ms += t0.elapsed_time(t1)
+        if step in (0, args.steps - 1):
+            hist.append((float(sdf_loss.detach()), float((norm.detach() - 1.0).abs().mean())))
+    torch.cuda.synchronize()
+    result = extract()
+    info = {"steps": args.steps, "points_per_step": args.n, "levels": args.levels, "log2_T": args.log2_T, "max_res": args.max_res,
+            "target_resolution": args.target_resolution, "resolution": args.resolution, "target_faces": int(target.faces.shape[0]),
+            "sdf_loss_first": hist[0][0], "sdf_loss_last": hist[-1][0], "eikonal_error_first": hist[0][1], "eikonal_error_last": hist[-1][1],
+            "surface_distance_untrained": untrained, "surface_distance": compare(result),
+            "topology_target": topology(target), "topology_result": topology(result),
+            "query_ms_per_step": query_ms / max(args.steps, 1)}
+    print(json.dumps(info))
+    return dict(info, target=target, result=result, field=field)
+
+
+if __name__ == "__main__":
+    main()

@@ -713,6 +713,33 @@ int ngp_mesh_emit(const float* values, int nx, int ny, int nz, float iso, int si
                   const float* h /*[3], host*/, const void* workspace, float* vertices, float* normals /* may be NULL */, int32_t* faces,
                   void* stream);
 
+/* ---- distance to a triangle mesh: a bounding-volume hierarchy and a nearest-face query (csrc/mesh_sdf.hip) ----
+ * vertices f32 [V,3], faces int32 [*,3] (indices trusted: the caller checks their range), order int32 [n_faces]: the faces the tree
+ * holds, in the order it holds them (any permutation of a subset of the rows of `faces`; the package sorts by the Morton code of the
+ * centroid).  Leaf k = sorted positions [k leaf_size, (k + 1) leaf_size), padded to P = a power of two leaves; node i of the implicit
+ * complete binary tree has the children 2 i + 1 and 2 i + 2, leaf k is node P - 1 + k.  boxes: f32 [2 P - 1, 6] = (lo xyz, hi xyz),
+ * every leaf box widened outwards by 2^-18 of its longest side and one ulp; a node without faces has lo = +inf, hi = -inf.
+ * bvh_bytes : the size of `boxes`; -1 for n_faces < 1, n_faces >= 2^31, a leaf_size outside 1..NGP_MESH_SDF_MAX_LEAF or more than
+ *             2^24 leaves (the walk keeps one bit per level)
+ * bvh_build : fills boxes, one launch per level, no atomics: the same mesh and order give the same bytes
+ * sdf_query : one launch, one lane per point.  Per point the face that minimises the squared distance in f32 (closest point by the
+ *             Voronoi regions of Ericson 5.1.5, the formula in csrc/mesh_sdf.hip; a face whose distance is NaN never wins), written as
+ *             sdf [n] = s sqrt(dist2), closest [n,3], face [n] (a row of `faces`, i.e. the caller's numbering), feature [n]: 0 interior,
+ *             1 / 2 / 3 edge ab / bc / ca, 4 / 5 / 6 vertex a / b / c.  closest, face, feature may be NULL.  edge_normals f32 [*,3,3]
+ *             (per row of `faces`, per edge) and vertex_normals f32 [V,3]: the pseudonormals; s = +1 if n . (x - closest) >= 0 else -1
+ *             with n = cross(b - a, c - a), the edge's or the vertex's by the feature.  Both NULL: unsigned, s = +1.  A result depends
+ *             on its point and the mesh alone.  If no face has a distance (all NaN): sdf +inf, closest = the point, face -1.
+ * All return -1 without a launch for a null required pointer, a size bvh_bytes refuses, n < 0 or exactly one of the two normal
+ * arrays; sdf_query returns 0 without a launch for n = 0 (points and sdf may then be null: an empty tensor has no address). */
+#define NGP_MESH_SDF_MAX_LEAF 8
+long long ngp_mesh_bvh_bytes(long long n_faces, int leaf_size);
+int ngp_mesh_bvh_build(const float* vertices, const int32_t* faces, const int32_t* order, int n_faces, int leaf_size, float* boxes,
+                       void* stream);
+int ngp_mesh_sdf_query(const float* points, int n, const float* vertices, const int32_t* faces, const int32_t* order, const float* boxes,
+                       int n_faces, int leaf_size, const float* edge_normals /* may be NULL */, const float* vertex_normals /* may be NULL */,
+                       float* sdf, float* closest /* may be NULL */, int32_t* face /* may be NULL */, int32_t* feature /* may be NULL */,
+                       void* stream);
+
 /* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
  * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
  * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],

@@ -152,3 +152,66 @@ def write_obj(path, mesh):
             fh.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist())
         else:
             fh.writelines("f %d %d %d\n" % tuple(r) for r in (f + 1).tolist())
+
+
+def read_ply(path):
+    """Reads exactly what write_ply writes -> Mesh of CPU tensors, bit for bit.  Any other header (ascii, big endian, other properties
+    or elements, polygons that are not triangles) raises ValueError."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if end < 0:
+        raise ValueError("%s: no PLY header" % path)
+    lines = data[:end].decode("ascii", "replace").split("\n")[:-1]
+    body = data[end + len(b"end_header\n"):]
+    xyz, nrm = ["property float %s" % p for p in "xyz"], ["property float %s" % p for p in ("nx", "ny", "nz")]
+    if len(lines) < 8 or lines[:2] != ["ply", "format binary_little_endian 1.0"] or not lines[2].startswith("element vertex ") \
+            or lines[3:6] != xyz or lines[-1] != "property list uchar int vertex_indices" or not lines[-2].startswith("element face ") \
+            or lines[6:-2] not in ([], nrm):
+        raise ValueError("%s: not the PLY layout write_ply produces (binary little endian, float x y z [nx ny nz], uchar/int faces)" % path)
+    try:
+        n_v, n_f = int(lines[2].split()[2]), int(lines[-2].split()[2])
+    except ValueError:
+        raise ValueError("%s: malformed element counts" % path) from None
+    cols = 3 + len(lines[6:-2])
+    if n_v < 0 or n_f < 0 or len(body) != 4 * cols * n_v + 13 * n_f:
+        raise ValueError("%s: the body holds %d bytes, the header announces %d" % (path, len(body), 4 * cols * n_v + 13 * n_f))
+    v = np.frombuffer(body, "<f4", cols * n_v).reshape(n_v, cols)
+    rows = np.frombuffer(body, np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), n_f, 4 * cols * n_v)
+    if n_f and (rows["n"] != 3).any():
+        raise ValueError("%s: a face that is not a triangle" % path)
+    t = lambda a: torch.from_numpy(np.array(a))                        # a copy: the buffer is read-only
+    return Mesh(t(v[:, :3]), t(rows["idx"].astype(np.int32)), t(v[:, 3:]) if cols == 6 else None)
+
+
+def read_obj(path):
+    """Reads exactly what write_obj writes -> Mesh of CPU tensors: `v x y z`, then `vn x y z` (as many as vertices) with `f a//a b//b
+    c//c`, or no normals with `f a b c`; `#` comments and blank lines are skipped.  Anything else raises ValueError."""
+    v, n, f = [], [], []
+    with open(path) as fh:
+        for no, line in enumerate(fh, 1):
+            w = line.split()
+            if not w or w[0].startswith("#"):
+                continue
+            try:
+                if w[0] in ("v", "vn") and len(w) == 4:
+                    (v if w[0] == "v" else n).append([float(x) for x in w[1:]])
+                elif w[0] == "f" and len(w) == 4:
+                    idx = []
+                    for c in w[1:]:
+                        a, sep, b = c.partition("//")
+                        if (sep and a != b) or bool(sep) != bool(n):
+                            raise ValueError
+                        idx.append(int(a))
+                    f.append(idx)
+                else:
+                    raise ValueError
+            except ValueError:
+                raise ValueError("%s:%d: not what write_obj produces: %r" % (path, no, line.strip())) from None
+    if n and len(n) != len(v):
+        raise ValueError("%s: %d normals for %d vertices" % (path, len(n), len(v)))
+    faces = np.asarray(f, np.int64).reshape(-1, 3) - 1
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(v)):
+        raise ValueError("%s: a face index outside 1..%d" % (path, len(v)))
+    t = lambda a, dt: torch.from_numpy(np.asarray(a, dt).reshape(-1, 3))
+    return Mesh(t(v, np.float32), torch.from_numpy(faces.astype(np.int32)), t(n, np.float32) if n else None)

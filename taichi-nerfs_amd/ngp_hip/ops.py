@@ -853,6 +853,63 @@ def mesh_emit(values, iso, sign, lo, h, workspace, n_vertices, n_faces, normals=
     return vertices, nrm, faces
 
 
+# ---------------------------------------------------------------------------------------------------- distance to a triangle mesh
+MESH_SDF_MAX_LEAF = _lib_mod._ABI.defines["NGP_MESH_SDF_MAX_LEAF"]
+
+
+def _mesh_sdf_mesh(vertices, faces, order, leaf_size):
+    """Shapes first (no device needed), then the devices -> (n_faces in the tree, bytes of its boxes)."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or order.dim() != 1:
+        raise ValueError("vertices must be [V,3], faces [T,3] and order [n_faces], got %s, %s, %s"
+                         % (tuple(vertices.shape), tuple(faces.shape), tuple(order.shape)))
+    if not 1 <= int(leaf_size) <= MESH_SDF_MAX_LEAF:
+        raise ValueError("leaf_size must be in 1..%d, got %r" % (MESH_SDF_MAX_LEAF, leaf_size))
+    if not 1 <= order.shape[0] <= faces.shape[0]:
+        raise ValueError("order must name between one and all of the %d faces, got %d" % (faces.shape[0], order.shape[0]))
+    _dev(vertices, torch.float32, "vertices"); _dev(faces, torch.int32, "faces"); _dev(order, torch.int32, "order")
+    need = _lib().ngp_mesh_bvh_bytes(order.shape[0], int(leaf_size))
+    if need < 0:
+        raise ValueError("%d faces in leaves of %d make a tree deeper than the walk's 24 levels: use a larger leaf_size"
+                         % (order.shape[0], leaf_size))
+    return int(order.shape[0]), need
+
+
+def mesh_bvh_build(vertices, faces, order, leaf_size=4):
+    """The box hierarchy of csrc/mesh_sdf.hip over the faces order [n_faces] names (rows of faces [T,3] int32, indices into vertices
+    [V,3] f32: TRUSTED, the caller has checked their range), in that order -> boxes f32 [2 P - 1, 6]."""
+    n_faces, need = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
+    boxes = torch.empty(need // 24, 6, device=vertices.device, dtype=torch.float32)
+    check(_lib().ngp_mesh_bvh_build(_ptr(vertices), _ptr(faces), _ptr(order), n_faces, int(leaf_size), _ptr(boxes), _stream()),
+          "ngp_mesh_bvh_build")
+    return boxes
+
+
+def mesh_sdf_query(points, vertices, faces, order, boxes, leaf_size=4, edge_normals=None, vertex_normals=None, details=True):
+    """Nearest face of every point [n,3] f32 -> (sdf [n], closest [n,3], face [n] int32, feature [n] int32); details=False: only sdf, the
+    others None (the same bits).  Signed iff edge_normals f32 [T,3,3] and vertex_normals f32 [V,3] are given (both or neither)."""
+    n_faces, need = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be [n,3], got %s" % (tuple(points.shape),))
+    if (edge_normals is None) != (vertex_normals is None):
+        raise ValueError("edge_normals and vertex_normals go together: both for the signed distance, neither for the unsigned")
+    _dev(points, torch.float32, "points"); _dev(boxes, torch.float32, "boxes")
+    if boxes.numel() * 4 != need:
+        raise ValueError("boxes holds %d bytes, the tree of %d faces in leaves of %d needs %d" % (boxes.numel() * 4, n_faces, leaf_size, need))
+    if edge_normals is not None:
+        _dev(edge_normals, torch.float32, "edge_normals"); _dev(vertex_normals, torch.float32, "vertex_normals")
+        if tuple(edge_normals.shape) != (faces.shape[0], 3, 3) or tuple(vertex_normals.shape) != tuple(vertices.shape):
+            raise ValueError("edge_normals must be [T,3,3] and vertex_normals [V,3]")
+    n = points.shape[0]
+    sdf = torch.empty(n, device=points.device, dtype=torch.float32)
+    closest = torch.empty(n, 3, device=points.device, dtype=torch.float32) if details else None
+    face = torch.empty(n, device=points.device, dtype=torch.int32) if details else None
+    feature = torch.empty(n, device=points.device, dtype=torch.int32) if details else None
+    check(_lib().ngp_mesh_sdf_query(_ptr(points), n, _ptr(vertices), _ptr(faces), _ptr(order), _ptr(boxes), n_faces, int(leaf_size),
+                                    _ptr(edge_normals), _ptr(vertex_normals), _ptr(sdf), _ptr(closest), _ptr(face), _ptr(feature),
+                                    _stream()), "ngp_mesh_sdf_query")
+    return sdf, closest, face, feature
+
+
 # ---------------------------------------------------------------------------------------------------- surface rendering
 def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
     _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
