@@ -17,6 +17,20 @@ def shard_rays(n_total, rank, world):
     return start, start + base + (1 if rank < rem else 0)
 
 
+def all_reduce_avg(t, world, group=None, async_op=False):
+    """t <- element-wise mean of t over the ranks.  RCCL: all_reduce(AVG); other backends (gloo has no AVG): all_reduce(SUM), then
+    t / world.  async_op: starts the collective and returns finish(), which waits for it and divides."""
+    avg = dist.get_backend(group) == "nccl"
+    work = dist.all_reduce(t, op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM, group=group, async_op=async_op)
+
+    def finish():
+        if async_op:
+            work.wait()
+        if not avg:
+            t.div_(world)
+    return finish if async_op else finish()
+
+
 class GradReducer:
     """Averages .grad of every trainable parameter across ranks.
 
@@ -29,16 +43,9 @@ class GradReducer:
         self.world = world if world is not None else dist.get_world_size(group)
         self.big_numel = big_numel
         self.group = group
-        self._avg = None
 
     def _reduce(self, t):
-        if self._avg is None:
-            self._avg = dist.get_backend(self.group) == "nccl"
-        if self._avg:
-            dist.all_reduce(t, op=dist.ReduceOp.AVG, group=self.group)
-        else:                                   # gloo (CPU tests) has no AVG
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
-            t.div_(self.world)
+        all_reduce_avg(t, self.world, self.group)
 
     @torch.no_grad()
     def all_reduce(self):
@@ -68,8 +75,8 @@ def reduce_scatter_avg(out, inp, rank, world, group=None):
     if dist.get_backend(group) == "nccl":
         dist.reduce_scatter_tensor(out, inp, op=dist.ReduceOp.AVG, group=group)
     else:
-        dist.all_reduce(inp, op=dist.ReduceOp.SUM, group=group)
-        out.copy_(inp[rank * out.numel():(rank + 1) * out.numel()]).div_(world)
+        all_reduce_avg(inp, world, group)                    # (the whole of inp becomes the mean: callers clear or drop it)
+        out.copy_(inp[rank * out.numel():(rank + 1) * out.numel()])
     return out
 
 
@@ -155,18 +162,15 @@ class GroupedExchange:
             g.comm.copy_(inp)
             inp, out = g.comm, g.comm_shard
         rank, world, c = self.rank, self.world, g.c
+        post = lambda: out.copy_(inp[rank * c:(rank + 1) * c])
         if self.stub:
-            work, post = None, (lambda: out.copy_(inp[rank * c:(rank + 1) * c]))
+            wait = lambda: None
         elif self._nccl():
-            work, post = dist.reduce_scatter_tensor(out, inp, op=dist.ReduceOp.AVG, group=self.group, async_op=True), None
-        else:                                      # gloo (functional tests): no AVG, no reduce-scatter on its CUDA path
-            work = dist.all_reduce(inp, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-            post = lambda: out.copy_(inp[rank * c:(rank + 1) * c]).div_(world)
+            wait, post = dist.reduce_scatter_tensor(out, inp, op=dist.ReduceOp.AVG, group=self.group, async_op=True).wait, None
+        else:                                      # gloo (functional tests): no reduce-scatter on its CUDA path
+            wait = all_reduce_avg(inp, world, self.group, async_op=True)
 
         def finish():
-            def wait():
-                if work is not None:
-                    work.wait()
             self.timed("wait_reduce_scatter_group%d" % g.index, wait)
             if post is not None:
                 post()

@@ -249,6 +249,15 @@ class FusedTrainRender(torch.autograd.Function):
         return (None, None, None, (dtable.float() if half else dtable).view(ctx.table_shape), *grads, None)
 
 
+def concentrated_scene(exp_step_factor, cascades):
+    """True for scenes that fill a small part of their box -- multi-cascade or exponentially stepped -- whose scatter-add runs on
+    the NGP_BWD_PLAN_CONCENTRATED task plan (RenderConfig and FusedTrainer both ask here); NGP_EXPERIMENT bwd_concentrated=0 / 1
+    overrides."""
+    from . import experiment as _exp
+    conc = _exp.get("bwd_concentrated")
+    return (conc == "1") if conc is not None else (float(exp_step_factor) > 0 or int(cascades) > 1)
+
+
 class RenderConfig:
     """Scalars + handles the fused step needs from the model (captured once per call; plain Python values so a
     captured hipGraph bakes them in)."""
@@ -268,9 +277,7 @@ class RenderConfig:
         # the level table as every kernel gets it; for scenes that fill a small part of their box (multi-cascade / exponentially stepped:
         # the Garden recipe, scripts/train_360_v2_garden.sh) it carries the scatter-add's concentrated-scene plan bit, so that the
         # drop-in render() runs the same task plan FusedTrainer picks (VERDICT r5 missing item 7).  NGP_EXPERIMENT bwd_concentrated=0 / 1 overrides.
-        from . import experiment as _exp
-        conc = _exp.get("bwd_concentrated")
-        concentrated = (conc == "1") if conc is not None else (self.exp_step_factor > 0 or self.cascades > 1)
+        concentrated = concentrated_scene(self.exp_step_factor, self.cascades)
         self.levels = model.pos_encoder.levels_struct.with_plan(_lib_mod.BWD_PLAN_CONCENTRATED if concentrated else 0)
         self.lo = -float(model.scale)            # xyz_min / xyz_max of reference networks.py:57-58
         self.hi = float(model.scale)

@@ -3,6 +3,7 @@ torch HIP stream.  No autograd here (that lives in modules/), no CPU path: every
 tensors and raises otherwise."""
 import ctypes
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -139,36 +140,46 @@ def march_train_fused(rays_o, rays_d, hits_t, density_bitfield, noise, cascades,
         _dev(noise, torch.float32, "noise")
     n = rays_o.shape[0]
     dev = rays_o.device
-    L = _lib()
-    stage = MarchArena.get(dev, n, int(max_samples))
     cap = n * int(max_samples) if capacity is None else int(capacity)
-    rays_a = torch.empty(n, 3, device=dev, dtype=torch.int32)
-    total = torch.zeros(1, device=dev, dtype=torch.int32)
-    ctr = torch.zeros(2, device=dev, dtype=torch.int32)
-    xyzs, dirs = torch.empty(cap, 3, device=dev, dtype=torch.float32), torch.empty(cap, 3, device=dev, dtype=torch.float32)
-    deltas, ts = torch.empty(cap, device=dev, dtype=torch.float32), torch.empty(cap, device=dev, dtype=torch.float32)
+    if (shape is not None or noise is None) and cap < n * int(max_samples):
+        raise ValueError("the %s form writes into arrays of n * max_samples rows" % ("shaped" if shape is not None else "seeded"))
+    f32 = dict(device=dev, dtype=torch.float32)
+    M = SimpleNamespace(stage=MarchArena.get(dev, n, int(max_samples)), rays_a=torch.empty(n, 3, device=dev, dtype=torch.int32),
+                        total=torch.zeros(1, device=dev, dtype=torch.int32), ctr=torch.zeros(2, device=dev, dtype=torch.int32),
+                        xyzs=torch.empty(cap, 3, **f32), dirs=torch.empty(cap, 3, **f32), deltas=torch.empty(cap, **f32),
+                        ts=torch.empty(cap, **f32))
     coarse = coarse_bitfield(density_bitfield, cascades, grid_size)
-    if shape is not None:
-        if cap < n * int(max_samples):
-            raise ValueError("the shaped form writes into arrays of n * max_samples rows")
-        check(L.ngp_march_train_fused_shaped(_ptr(rays_o), _ptr(rays_d), _ptr(hits_t), _ptr(density_bitfield), _ptr(coarse), _ptr(noise),
-                                             int(seed or 0), int(cascades), int(grid_size), float(scale), float(exp_step_factor),
-                                             int(max_samples), n, int(shape[0]), int(shape[1]), _ptr(stage), _ptr(ctr), _ptr(rays_a),
-                                             _ptr(total), _ptr(xyzs), _ptr(dirs), _ptr(deltas), _ptr(ts), _stream()),
+    launch_march_train(_lib(), M, rays_o, rays_d, hits_t, density_bitfield, coarse, noise, seed or 0, cascades, grid_size, scale,
+                       exp_step_factor, max_samples, shape=shape, cap=cap)
+    return M.rays_a, M.xyzs, M.dirs, M.deltas, M.ts, M.total[0], M.ctr
+
+
+def launch_march_train(L, M, rays_o, rays_d, hits_t, bitfield, coarse, noise, seed, cascades, grid_size, scale, exp_step_factor,
+                       max_samples, shape=None, cap=None, ray_order=False):
+    """The training march into buffers the caller owns (M.stage, .ctr, .rays_a, .total, .xyzs, .dirs, .deltas, .ts; .counts for
+    ray_order), on the current stream -- the one place that picks the ngp_march_train_* entry:
+      ray_order      the count / scan / write chain (rays packed in ray order; needs a noise vector);
+      shape          ngp_march_train_fused_shaped (waves per block, idle LDS bytes; jitter from `noise`, else from `seed`);
+      noise is None  ngp_march_train_fused_rng: the jitter drawn in the kernel from `seed`;
+      otherwise      ngp_march_train_fused on `noise`, or _fused_cap when the outputs hold `cap` rows only."""
+    n, st = rays_o.shape[0], _stream()
+    rays = (_ptr(rays_o), _ptr(rays_d), _ptr(hits_t), _ptr(bitfield), _ptr(coarse))
+    geom = (int(cascades), int(grid_size), float(scale), float(exp_step_factor), int(max_samples), n)
+    out = (_ptr(M.stage), _ptr(M.ctr), _ptr(M.rays_a), _ptr(M.total), _ptr(M.xyzs), _ptr(M.dirs), _ptr(M.deltas), _ptr(M.ts), st)
+    if ray_order:
+        check(L.ngp_march_train_count_ex(*rays, _ptr(noise), *geom, _ptr(M.stage), _ptr(M.counts), st), "ngp_march_train_count_ex")
+        check(L.ngp_march_train_scan(_ptr(M.counts), n, _ptr(M.rays_a), _ptr(M.total), st), "ngp_march_train_scan")
+        check(L.ngp_march_train_write(_ptr(rays_o), _ptr(rays_d), _ptr(M.rays_a), _ptr(M.stage), int(max_samples), n,
+                                      _ptr(M.xyzs), _ptr(M.dirs), _ptr(M.deltas), _ptr(M.ts), st), "ngp_march_train_write")
+    elif shape is not None:
+        check(L.ngp_march_train_fused_shaped(*rays, _ptr(noise), int(seed), *geom, int(shape[0]), int(shape[1]), *out),
               "ngp_march_train_fused_shaped")
     elif noise is None:
-        if cap < n * int(max_samples):
-            raise ValueError("the seeded form writes into arrays of n * max_samples rows")
-        check(L.ngp_march_train_fused_rng(_ptr(rays_o), _ptr(rays_d), _ptr(hits_t), _ptr(density_bitfield), _ptr(coarse), int(seed),
-                                          int(cascades), int(grid_size), float(scale), float(exp_step_factor), int(max_samples), n,
-                                          _ptr(stage), _ptr(ctr), _ptr(rays_a), _ptr(total), _ptr(xyzs), _ptr(dirs), _ptr(deltas), _ptr(ts),
-                                          _stream()), "ngp_march_train_fused_rng")
+        check(L.ngp_march_train_fused_rng(*rays, int(seed), *geom, *out), "ngp_march_train_fused_rng")
+    elif cap is None:
+        check(L.ngp_march_train_fused(*rays, _ptr(noise), *geom, *out), "ngp_march_train_fused")
     else:
-        check(L.ngp_march_train_fused_cap(_ptr(rays_o), _ptr(rays_d), _ptr(hits_t), _ptr(density_bitfield), _ptr(coarse), _ptr(noise),
-                                          int(cascades), int(grid_size), float(scale), float(exp_step_factor), int(max_samples), n, cap,
-                                          _ptr(stage), _ptr(ctr), _ptr(rays_a), _ptr(total), _ptr(xyzs), _ptr(dirs), _ptr(deltas), _ptr(ts),
-                                          _stream()), "ngp_march_train_fused_cap")
-    return rays_a, xyzs, dirs, deltas, ts, total[0], ctr
+        check(L.ngp_march_train_fused_cap(*rays, _ptr(noise), *geom, int(cap), *out), "ngp_march_train_fused_cap")
 
 
 def rng_uniform(seed, n, device="cuda"):

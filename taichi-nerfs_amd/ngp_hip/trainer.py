@@ -27,12 +27,54 @@ import torch.distributed as dist
 
 from . import experiment as _exp
 from . import lib as _lib_mod
-from .fused import RenderConfig, TrainArena
+from .dist import all_reduce_avg
+from .fused import RenderConfig, TrainArena, concentrated_scene
 from .lib import check
-from .ops import MLP_N_WEIGHTS, _ptr, _stream
+from .ops import MLP_N_WEIGHTS, _ptr, _stream, launch_march_train, rng_uniform
 
 _SF_LOSS_SCALE, _SF_LOSS = 0, 5
 _SI_ITER, _SI_OPT_STEP, _SI_FOUND_INF, _SI_SKIPPED = 0, 1, 3, 5
+
+
+class _PrefetchPoint:
+    """Where in the step the next batch's march goes onto the side stream.  _launch arms it with the march and a position; the step
+    calls reach(p) at each position in step order and the first p >= at issues the march, once.  Positions:
+    0 start of the step, 1 behind the hash gather (chunked forward: round 0's), 2 behind the MLP forward, 2.5 in front of the
+    scatter-add's prepass, 2.75 in front of the MLP backward, 3 in front of the scatter-add, 4 behind it (overlapped exchange:
+    behind the start of the last group's reduce-scatter).  Unarmed (no prefetch, or already issued) it does nothing."""
+    __slots__ = ("at", "action")
+
+    def __init__(self):
+        self.at, self.action = 0.0, None
+
+    def arm(self, at, action):
+        self.at, self.action = min(at, 4), action         # (4 is the last position of the step: nothing armed is left unissued)
+
+    def reach(self, p):
+        if self.action is not None and p >= self.at:
+            action, self.action = self.action, None
+            action()
+
+
+class _Step:
+    """What one step's launches share, built once by FusedTrainer._shade: the march set M, the arena A, the render configuration,
+    the stream, the prefetch point, the per-ray outputs; the backward's sample count and live list (cnt, live_idx), the level table
+    with the step's plan bits (lvp) and the scatter-add's workspace (ws) are filled in as the step gets to them."""
+    __slots__ = ("M", "A", "cfg", "st", "P", "n", "pf", "found", "vr_per_ray", "opacity", "depth", "rgb", "sq_err", "cnt", "live_idx",
+                 "lvp", "ws")
+
+    def __init__(self, M, A, cfg, st, P, n, pf, found, dev):
+        self.M, self.A, self.cfg, self.st, self.P, self.n, self.pf, self.found = M, A, cfg, st, P, n, pf, found
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.vr_per_ray = torch.empty(n, device=dev, dtype=torch.int32)
+        self.opacity, self.depth, self.rgb = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, 3, **f32)
+        self.sq_err = torch.empty(n, **f32)
+        self.cnt = self.live_idx = self.lvp = self.ws = None
+
+    def result(self):
+        M = self.M
+        return {"rm_samples": M.total, "vr_per_ray": self.vr_per_ray, "rgb": self.rgb, "opacity": self.opacity, "depth": self.depth,
+                "rays_a": M.rays_a, "deltas": M.deltas, "ts": M.ts, "sq_err": self.sq_err}
 
 
 class FusedTrainer:
@@ -264,7 +306,6 @@ class FusedTrainer:
         # 0.556 at 3, 0.560 at 0, 0.564 at 1 (not prefetched: 0.570).  Then the march became ONE launch (ngp_march_train_fused,
         # ~55 us) and the live list a by-product of the composite kernel; 3 runs x 400 steps each, no per-kernel events, at
         # 350 k live: 0.525 ms at 3 (under the scatter-add), 0.532 at 0, 0.538 at 2, 0.553 at 1, not prefetched 0.548
-        import os as _os
         # (with world > 1 the default is 4: the march then runs underneath the gradient exchange -- RCCL's kernels occupy a few
         # workgroups and wait on xGMI -- instead of competing with the VALU-bound kernels of the step for issue slots)
         self._prefetch_at = float(_exp.get("prefetch_at", "3" if self.world == 1 else "4"))
@@ -297,7 +338,12 @@ class FusedTrainer:
             self.copy16_store = torch.zeros(self.nt_pad, device=dev, dtype=torch.float16)
             enc._f16, enc._f16_ver = self.copy16_store[:nt].view(enc.hash_table.shape), None
             self.table_f16 = enc.table_f16().view(-1)
-        self._master_stale = False            # sharded + 16-bit copy: the fp32 master of the other ranks' shards is gathered lazily
+        # the 16-bit copy as every launch gets it: its storage kind (0 none / 1 bf16 / 2 fp16), its [:nt] view, and the table the
+        # forward gathers from
+        self._kind16 = 2 if self.half else (1 if self.table_bf16 is not None else 0)
+        self._copy16 = self.copy16_store[:nt] if self.copy16_store is not None else None
+        self._fwd_table = self.table_f16 if self.half else (self.table_bf16 if self.table_bf16 is not None else self.table)
+        self._master_stale = False           # sharded + 16-bit copy: the fp32 master of the other ranks' shards is gathered lazily
         # NGP_EXPERIMENT comm_overlap=1 (sharded exchange, fp32 gradient, LDS-sliced scatter-add): the scatter-add is issued as one launch per
         # LEVEL GROUP (NGP_EXPERIMENT comm_groups = first level of each group in launch order, default "8,0": levels 8-15, then 0-7) and a
         # group's reduce-scatter travels while the next group is still being accumulated; every rank owns the rank-th 1/world of
@@ -320,8 +366,7 @@ class FusedTrainer:
         # Multi-cascade / exponentially stepped scenes fill a small part of their box: the scatter-add's plan then treats the coarse
         # hashed levels like dense ones (NGP_BWD_PLAN_CONCENTRATED; C3: the launch 2.5 -> 1.7 ms beside the march, which then no
         # longer fits under it as 16-wave blocks: 4-wave blocks, profiles/r05_bench_garden_c3_concentrated.txt).  NGP_EXPERIMENT bwd_concentrated=0 / 1 overrides.
-        conc = _exp.get("bwd_concentrated")
-        self._concentrated = (conc == "1") if conc is not None else (float(exp_step_factor) > 0 or int(model.cascades) > 1)
+        self._concentrated = concentrated_scene(exp_step_factor, model.cascades)
         self.set_deterministic(os.environ.get("NGP_DETERMINISTIC", "0") == "1")
 
     def _init_exchange(self, model, dev, exchange):
@@ -458,47 +503,23 @@ class FusedTrainer:
         return coarse
 
     def _march(self, M, rays_o, rays_d, cfg, A, coarse=None, noise=None, shape=None):
-        """ray-AABB + count/scan/write into march set M on the CURRENT stream."""
-        L, st, n = self.L, _stream(), rays_o.shape[0]
+        """The training march into march set M on the CURRENT stream (slab test inline); which entry: ops.launch_march_train."""
+        n = rays_o.shape[0]
         if coarse is None:
             coarse = self._coarse_bits(cfg, A)
-        if shape is not None and noise is None and self.march_fused and self._march_rng and not self.deterministic:
-            seed = int(torch.randint(0, 2**62, (), dtype=torch.int64))
-            check(L.ngp_march_train_fused_shaped(_ptr(rays_o), _ptr(rays_d), _ptr(None), _ptr(cfg.bitfield), _ptr(coarse), _ptr(None), seed,
-                                                 cfg.cascades, cfg.grid_size, cfg.scale, cfg.exp_step_factor, cfg.max_samples, n,
-                                                 int(shape[0]), int(shape[1]), _ptr(M.stage), _ptr(M.ctr), _ptr(M.rays_a), _ptr(M.total),
-                                                 _ptr(M.xyzs), _ptr(M.dirs), _ptr(M.deltas), _ptr(M.ts), st), "ngp_march_train_fused_shaped")
-            return
-        if noise is None and self.deterministic:
-            # same counter-based jitter as the one-launch march draws in-kernel, as an explicit vector for the ray-order chain
-            from .ops import rng_uniform
-            noise = rng_uniform(int(torch.randint(0, 2**62, (), dtype=torch.int64)), n, self.dev)
-        if noise is None and self.march_fused and self._march_rng:
+        ray_order = self.deterministic or not self.march_fused     # count / scan / write chain (NGP_EXPERIMENT march_fused=0)
+        seed = 0
+        if noise is None and (self.deterministic or (self.march_fused and self._march_rng)):
             # the per-ray jitter (torch.rand_like, ray_march.py:138) is drawn inside the march kernel from a counter-based
             # generator keyed by (seed, ray); the seed comes from torch's CPU generator, so torch.manual_seed() still fixes the
             # jitter sequence -- and no uniform_ kernel sits on the (side) stream in front of the march
             seed = int(torch.randint(0, 2**62, (), dtype=torch.int64))
-            check(L.ngp_march_train_fused_rng(_ptr(rays_o), _ptr(rays_d), _ptr(None), _ptr(cfg.bitfield), _ptr(coarse), seed,
-                                              cfg.cascades, cfg.grid_size, cfg.scale, cfg.exp_step_factor, cfg.max_samples, n,
-                                              _ptr(M.stage), _ptr(M.ctr), _ptr(M.rays_a), _ptr(M.total), _ptr(M.xyzs), _ptr(M.dirs),
-                                              _ptr(M.deltas), _ptr(M.ts), st), "ngp_march_train_fused_rng")
-            return
-        if noise is None:
+            if self.deterministic:                                 # the same jitter as an explicit vector for the ray-order chain
+                noise = rng_uniform(seed, n, self.dev)
+        elif noise is None:
             noise = torch.rand(n, device=self.dev, dtype=torch.float32)                     # ray_march.py:138
-        if self.march_fused and not self.deterministic:
-            # one launch: count, block-wise allocation of the output ranges (rays in block-completion order, like the reference's
-            # atomic packing), expansion.  NGP_EXPERIMENT march_fused=0: the count / scan / write chain (rays packed in ray order)
-            check(L.ngp_march_train_fused(_ptr(rays_o), _ptr(rays_d), _ptr(None), _ptr(cfg.bitfield), _ptr(coarse), _ptr(noise),
-                                          cfg.cascades, cfg.grid_size, cfg.scale, cfg.exp_step_factor, cfg.max_samples, n,
-                                          _ptr(M.stage), _ptr(M.ctr), _ptr(M.rays_a), _ptr(M.total), _ptr(M.xyzs), _ptr(M.dirs),
-                                          _ptr(M.deltas), _ptr(M.ts), st), "ngp_march_train_fused")
-            return
-        check(L.ngp_march_train_count_ex(_ptr(rays_o), _ptr(rays_d), _ptr(None), _ptr(cfg.bitfield), _ptr(coarse), _ptr(noise),
-                                         cfg.cascades, cfg.grid_size, cfg.scale, cfg.exp_step_factor, cfg.max_samples, n,
-                                         _ptr(M.stage), _ptr(M.counts), st), "ngp_march_train_count_ex")   # slab test inline
-        check(L.ngp_march_train_scan(_ptr(M.counts), n, _ptr(M.rays_a), _ptr(M.total), st), "ngp_march_train_scan")
-        check(L.ngp_march_train_write(_ptr(rays_o), _ptr(rays_d), _ptr(M.rays_a), _ptr(M.stage), cfg.max_samples, n,
-                                      _ptr(M.xyzs), _ptr(M.dirs), _ptr(M.deltas), _ptr(M.ts), st), "ngp_march_train_write")
+        launch_march_train(self.L, M, rays_o, rays_d, None, cfg.bitfield, coarse, noise, seed, cfg.cascades, cfg.grid_size, cfg.scale,
+                           cfg.exp_step_factor, cfg.max_samples, shape=shape if noise is None else None, ray_order=ray_order)
 
     def _launch(self, rays_o, rays_d, target, prefetch=None, src=None, src_next=None, noise=None):
         self.finish_comm()                   # (overlapped exchange: the previous step's all-gathers, before the table is read)
@@ -525,7 +546,7 @@ class FusedTrainer:
         if not hit:
             self._march(M, rays_o, rays_d, cfg, A, noise=noise)
         M.ready, M.src, M.held = None, None, None
-        hook = None
+        pf = _PrefetchPoint()
         if prefetch is not None and (prefetch[0].shape != rays_o.shape or prefetch[1].shape != rays_d.shape):
             raise ValueError("prefetch rays must have the shape of the current batch (the two march buffers are sized per batch size)")
         if prefetch is not None:
@@ -543,7 +564,7 @@ class FusedTrainer:
                     at, shape, side = 3, (4, 0), self._side_low
             self._hook_at = at
 
-            def hook():
+            def issue():
                 start = self._ev_start
                 start.record(torch.cuda.current_stream())                   # everything that still reads `nxt` is before this
                 with torch.cuda.stream(side):
@@ -559,8 +580,8 @@ class FusedTrainer:
                               "ngp_copy_to_host_async")
                 nxt.src = None if src_next is None else (src_next[0], src_next[1], src_next[0]._version, src_next[1]._version)
                 nxt.held = prefetch          # (possibly temporaries of step()): alive until the set is consumed or re-marched
-            if at == 0 or self._graph is not None:
-                hook(); hook = None
+            pf.arm(at if self._graph is None else 0, issue)      # (graph mode: the march stays eager, at the start of the step)
+            pf.reach(0)
         # The fused live list relies on the counter of this step's parity being 0 at launch (the composite kernel of the PREVIOUS
         # step cleared it).  A step that raised after the flip below never ran that kernel: if the last launch did not complete,
         # clear both counters on the stream before going on (stale counts would be added to, silently).
@@ -571,7 +592,7 @@ class FusedTrainer:
         self._launch_incomplete = True
         cur, self._cur = self._cur, 1 - self._cur
         if self._graph is None:
-            stats = self._shade(M, n, target, cfg, A, hook)
+            stats = self._shade(M, n, target, cfg, A, pf)
             self._launch_incomplete = False
             return stats
         # hipGraph mode: the shading / backward / optimizer chain of march set `cur` is one graph launch
@@ -582,136 +603,142 @@ class FusedTrainer:
         if cur not in self._graph:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                stats = self._shade(M, n, self._static_target, cfg, A)
+                stats = self._shade(M, n, self._static_target, cfg, A, pf)
             self._graph[cur] = (g, stats)
         g, stats = self._graph[cur]
         g.replay()
         self._launch_incomplete = False
         return stats
 
-    def _shade(self, M, n, target, cfg, A, hook=None):
-        """Everything after the march: encode, MLPs, composite + loss, backward, [all-reduce], optimizer -- on the current stream."""
-        L, st, dev = self.L, _stream(), self.dev
-        i32 = dict(device=dev, dtype=torch.int32)
-        f32 = dict(device=dev, dtype=torch.float32)
-        rays_a, total = M.rays_a, M.total
-        vr_per_ray = torch.empty(n, **i32)
-        opacity, depth, rgb = torch.empty(n, **f32), torch.empty(n, **f32), torch.empty(n, 3, **f32)
-        sf, si = self.state_f, self.state_i
-        sq_err = torch.empty(n, **f32)
-        found = ctypes.c_void_p(si.data_ptr() + 4 * _SI_FOUND_INF)
-        P = self.enc_pairs
-        done = False
-        if self.chunked:
-            done, hook = self._shade_chunked(M, n, cfg, A, P, st, hook)
-        if not done:
-            hook = self._shade_all(M, cfg, A, P, st, total, hook)
-        par = M.index
-        live_total, live_next = self._live_pair[par:par + 1], self._live_pair[1 - par:2 - par]
-        fused_live = False
-        if self.distortion_loss_w > 0:
-            sq_err = self._composite_with_distortion(A, M, target, cfg, n, vr_per_ray, opacity, depth, rgb)
-        else:
-            # composite forward + MSE gradient + composite backward, one launch -- and, as a by-product, the compacted list of
-            # the LIVE samples (those in front of each ray's early-termination point; the rest have exact-zero gradients) that
-            # the MLP backward and the scatter-add run over
-            fused_live = self.live_backward and not self.deterministic      # (deterministic: the ray-ordered list of ngp_live_compact)
-            check(L.ngp_composite_train_fused_live(_ptr(A.sigmas), _ptr(A.rgbs), 1, _ptr(M.deltas), _ptr(M.ts), _ptr(rays_a),
-                                                   _ptr(target), self.bg, _ptr(sf), cfg.T_threshold, n, _ptr(vr_per_ray), _ptr(opacity),
-                                                   _ptr(depth), _ptr(rgb), _ptr(A.ws), _ptr(A.d_sigmas), _ptr(A.d_rgbs), _ptr(sq_err),
-                                                   _ptr(A.live_idx if fused_live else None), _ptr(live_total if fused_live else None),
-                                                   _ptr(live_next if fused_live else None), st), "ngp_composite_train_fused_live")
-        live_idx = A.live_idx
-        if self.live_backward and not fused_live:                 # (distortion-loss path: its composite is the operator chain)
-            if self.deterministic:                                # the ray-ORDERED list (every block scans all rays: 152 us at 65 536 rays)
-                check(L.ngp_live_compact(_ptr(rays_a), _ptr(vr_per_ray), n, _ptr(A.live_off(n)), _ptr(live_idx), _ptr(live_total), st),
-                      "ngp_live_compact")
-                live_next.zero_()
-            else:                                                 # block-completion order, one atomic per 64 rays; clears the other counter
-                check(L.ngp_live_list(_ptr(rays_a), _ptr(vr_per_ray), n, _ptr(live_idx), _ptr(live_total), _ptr(live_next), st),
-                      "ngp_live_list")
-        elif not fused_live:
-            live_next.zero_()
-        if self.live_backward:
-            cnt = live_total
-        else:
-            live_idx, cnt = None, total
-        # the scatter-add's prepass (hit bitmaps + compact positions; needs the positions and the live list only).  It used to run on
-        # a second stream underneath the MLP backward, but the two share the VALU (87 us overlapped vs 43 alone) and the
-        # cross-stream join cost 23 us between the prepass's end and the scatter-add's start: in line it is 17 us per step faster
-        sliced = self.hash_bwd == "sliced"          # (half2 encoder: same prepass, main pass with its fp16 arithmetic + fp16 table)
+    def _shade(self, M, n, target, cfg, A, pf):
+        """Everything after the march, on the current stream: forward (every sample, or chunked), composite + loss, the scatter-add's
+        prepass, MLP backward, then one of three tails: scatter-add with the optimizer in its flush; per-group scatter-add with the
+        exchange overlapped; scatter-add -> [exchange] -> prologue -> Adam.  pf.reach(p) marks the prefetch positions."""
+        L, st = self.L, _stream()
+        found = ctypes.c_void_p(self.state_i.data_ptr() + 4 * _SI_FOUND_INF)
+        s = _Step(M, A, cfg, st, self.enc_pairs, n, pf, found, self.dev)
+        if not (self.chunked and self._forward_chunked(s)):
+            self._forward_all(s)
+        self._composite_and_loss(s, target)
         det = self._scatter_mode()
-        lvp = self._lvp = cfg.levels.with_plan(det)           # the level table + this step's plan bits: prep, main and adam_prefix see the same
-        if hook is not None and self._hook_at == 2.5:
-            hook(); hook = None                                             # position 2.5: under the prepass, the MLP backward and the scatter-add
-        if sliced:
-            ws = A.sliced_ws(cfg.levels)
-            rc = L.ngp_hash_bwd_sliced_prep(_ptr(M.xyzs), ctypes.byref(lvp), A.cap, _ptr(cnt), _ptr(live_idx), 1, cfg.lo, cfg.hi,
-                                            _ptr(ws), ws.numel(), st)
-            if rc == -2:
-                # level table not expressible as <= 64 LDS slices per level: the float-atomic kernel from here on.  The overlapped
-                # exchange is built on per-level-group launches of the sliced kernel and shards the optimizer BY GROUP; falling
-                # through to the contiguous shard layout with the group layout still recorded would make state_dict() /
-                # sync_master() gather the wrong ranges (ADVICE r4) -- a trainer configured that way cannot continue
-                if self._groups is not None:
-                    raise RuntimeError("NGP_EXPERIMENT comm_overlap=1 needs the LDS-sliced scatter-add, which this level table does not fit "
-                                       "(ngp_hash_bwd_sliced_prep returned -2); unset NGP_EXPERIMENT comm_overlap")
-                self.hash_bwd, sliced = "atomic", False
-            else:
-                check(rc, "ngp_hash_bwd_sliced_prep")
-        # weight gradients leave the launch as per-block slabs (plain stores) instead of 256 x 9408 same-address float atomics (13 us
-        # of the launch); the slabs are added up by the prologue launch below, or -- when the gradient is needed before that (an
-        # exchange between ranks, compute_gradients) -- by a launch of its own right here
-        if hook is not None and self._hook_at == 2.75:
-            hook(); hook = None                                             # position 2.75: under the MLP backward and the scatter-add
-        if self._dw_atomic:                                   # NGP_EXPERIMENT mlp_dw=atomic: round 3's flush, for A/B runs
-            check(L.ngp_mlp_bwd_live(_ptr(A.enc), _ptr(M.dirs), _ptr(self.wpack), _ptr(A.d_sigmas), _ptr(A.d_rgbs), A.cap, _ptr(cnt),
-                                     _ptr(live_idx), P, _ptr(A.d_enc), _ptr(self.mlp_grad), found, st), "ngp_mlp_bwd_live")
-            n_parts = 0
-        else:
-            n_parts = L.ngp_mlp_bwd_live_parts(_ptr(A.enc), _ptr(M.dirs), _ptr(self.wpack), _ptr(A.d_sigmas), _ptr(A.d_rgbs), A.cap,
-                                               _ptr(cnt), _ptr(live_idx), P, _ptr(A.d_enc), _ptr(self.mlp_parts), found, st)
-            if n_parts <= 0:
-                check(n_parts or -1, "ngp_mlp_bwd_live_parts")
-        # ... summed by the head of the scatter-add launch (its first 147 persistent workgroups, ~2 us hidden in 200) on one GPU with
-        # the LDS-sliced scatter-add; by the prologue launch when the scatter-add is another kernel; by a launch of its own when the
-        # gradient is needed earlier (an exchange between ranks, compute_gradients)
-        single = self.world == 1 and not self._grads_only and n_parts > 0 and self._groups is None   # (overlapped tail: no slab hand-over)
-        reduce_in_scatter = single and sliced and not self.half and _exp.get("mlp_dw_reduce", "scatter") == "scatter"
-        reduce_in_prologue = single and not reduce_in_scatter
-        if n_parts > 0 and not single:
+        s.lvp = cfg.levels.with_plan(det)     # the level table + this step's plan bits: prep, main and adam_prefix see the same
+        pf.reach(2.5)                         # under the prepass, the MLP backward and the scatter-add
+        sliced = self._prepass(s)
+        pf.reach(2.75)                        # under the MLP backward and the scatter-add
+        n_parts = self._mlp_backward(s)
+        # The weight gradients' per-block slabs are summed by the head of the scatter-add launch (its first 147 persistent workgroups,
+        # ~2 us hidden in 200) on one GPU with the LDS-sliced scatter-add; by the prologue launch when the scatter-add is another
+        # kernel; by a launch of its own, right here, when the gradient is needed earlier (an exchange between ranks,
+        # compute_gradients; the overlapped tail has no slab hand-over either)
+        slabs_to = None
+        if self.world == 1 and not self._grads_only and n_parts > 0 and self._groups is None:
+            in_scatter = sliced and not self.half and _exp.get("mlp_dw_reduce", "scatter") == "scatter"
+            slabs_to = "scatter" if in_scatter else "prologue"
+        elif n_parts > 0:
             check(L.ngp_mlp_dw_reduce(_ptr(self.mlp_parts), n_parts, _ptr(self.mlp_grad), st), "ngp_mlp_dw_reduce")
-        if hook is not None and self._hook_at <= 3:
-            hook(); hook = None                                             # position 3: under the scatter-add and the optimizer
-        if reduce_in_scatter and self._flush_adam:
+        pf.reach(3)                           # under the scatter-add and the optimizer
+        npre = -1
+        if slabs_to == "scatter" and self._flush_adam:
             npre = self._adam_prefix.get(det)
             if npre is None:
-                npre = int(L.ngp_hash_bwd_sliced_adam_prefix(ctypes.byref(lvp)))
+                npre = int(L.ngp_hash_bwd_sliced_adam_prefix(ctypes.byref(s.lvp)))
                 npre = self._adam_prefix[det] = npre if npre % 4 == 0 else -2
-            if npre >= 0:
-                return self._tail_flush_adam(A, M, cfg, cnt, P, ws, n_parts, st, hook, total, vr_per_ray, rgb, opacity, depth, sq_err, npre)
-        if self._groups is not None and sliced and not self._grads_only:
-            self._tail_overlapped(A, cfg, cnt, P, ws, found, st, hook, None)
-            return {"rm_samples": total, "vr_per_ray": vr_per_ray, "rgb": rgb, "opacity": opacity, "depth": depth, "rays_a": rays_a,
-                    "deltas": M.deltas, "ts": M.ts, "sq_err": sq_err}
-        if reduce_in_scatter:
-            check(L.ngp_hash_bwd_sliced_main_slabs(_ptr(A.d_enc), ctypes.byref(lvp), A.cap, _ptr(cnt), P, _ptr(self.table_grad),
-                                                   0, found, _ptr(ws), ws.numel(), _ptr(self.mlp_parts), n_parts,
-                                                   _ptr(self.mlp_grad), st), "ngp_hash_bwd_sliced_main_slabs")
-        elif self.half and sliced:
-            check(L.ngp_hash_bwd_sliced_main_f16(_ptr(A.d_enc), ctypes.byref(lvp), A.cap, _ptr(cnt), P, _ptr(self.table_grad), found,
-                                                 _ptr(ws), ws.numel(), st), "ngp_hash_bwd_sliced_main_f16")
-        elif self.half:
-            check(L.ngp_hash_bwd_f16_live(_ptr(M.xyzs), _ptr(A.d_enc), ctypes.byref(cfg.levels), A.cap, _ptr(cnt), _ptr(live_idx), 1,
-                                          cfg.lo, cfg.hi, P, _ptr(self.table_grad), found, st), "ngp_hash_bwd_f16_live")
-        elif sliced:
-            check(L.ngp_hash_bwd_sliced_main(_ptr(A.d_enc), ctypes.byref(lvp), A.cap, _ptr(cnt), P, _ptr(self.table_grad), found,
-                                             _ptr(ws), ws.numel(), st), "ngp_hash_bwd_sliced_main")
+        if npre >= 0:
+            self._tail_flush_adam(s, n_parts, npre)
+        elif self._groups is not None and sliced and not self._grads_only:
+            self._tail_overlapped(s)
         else:
-            check(L.ngp_hash_bwd_f32_live(_ptr(M.xyzs), _ptr(A.d_enc), ctypes.byref(cfg.levels), A.cap, _ptr(cnt), _ptr(live_idx), 1,
-                                          cfg.lo, cfg.hi, P, _ptr(self.table_grad), found, st), "ngp_hash_bwd_f32_live")
-        if hook is not None:
-            hook(); hook = None                                             # position 4: under the gradient exchange + optimizer
+            self._tail_plain(s, sliced, n_parts, slabs_to)
+        return s.result()
+
+    def _composite_and_loss(self, s, target):
+        """Composite + MSE [+ distortion] and their gradients w.r.t. sigmas / rgbs; leaves the samples the backward runs over in
+        s.live_idx / s.cnt: the LIVE ones (in front of each ray's early-termination point; the rest have exact-zero gradients),
+        or every marched one (NGP_EXPERIMENT live_backward=0)."""
+        L, st, M, A, n = self.L, s.st, s.M, s.A, s.n
+        par, distortion = M.index, self.distortion_loss_w > 0
+        live_total, live_next = self._live_pair[par:par + 1], self._live_pair[1 - par:2 - par]
+        # composite forward + MSE gradient + composite backward in one launch has the live list as a by-product (block-completion
+        # order); not with the distortion loss (its composite is the operator chain) nor in deterministic mode (ray-ordered list)
+        fused_live = self.live_backward and not self.deterministic and not distortion
+        if distortion:
+            self._composite_with_distortion(s, target)
+        else:
+            lst = (A.live_idx, live_total, live_next) if fused_live else (None, None, None)
+            check(L.ngp_composite_train_fused_live(_ptr(A.sigmas), _ptr(A.rgbs), 1, _ptr(M.deltas), _ptr(M.ts), _ptr(M.rays_a),
+                                                   _ptr(target), self.bg, _ptr(self.state_f), s.cfg.T_threshold, n, _ptr(s.vr_per_ray),
+                                                   _ptr(s.opacity), _ptr(s.depth), _ptr(s.rgb), _ptr(A.ws), _ptr(A.d_sigmas),
+                                                   _ptr(A.d_rgbs), _ptr(s.sq_err), _ptr(lst[0]), _ptr(lst[1]), _ptr(lst[2]), st),
+                  "ngp_composite_train_fused_live")
+        if fused_live:
+            pass
+        elif not self.live_backward:
+            live_next.zero_()
+        elif self.deterministic:                                  # the ray-ORDERED list (every block scans all rays: 152 us at 65 536 rays)
+            check(L.ngp_live_compact(_ptr(M.rays_a), _ptr(s.vr_per_ray), n, _ptr(A.live_off(n)), _ptr(A.live_idx), _ptr(live_total), st),
+                  "ngp_live_compact")
+            live_next.zero_()
+        else:                                                     # block-completion order, one atomic per 64 rays; clears the other counter
+            check(L.ngp_live_list(_ptr(M.rays_a), _ptr(s.vr_per_ray), n, _ptr(A.live_idx), _ptr(live_total), _ptr(live_next), st),
+                  "ngp_live_list")
+        s.live_idx, s.cnt = (A.live_idx, live_total) if self.live_backward else (None, M.total)
+
+    def _prepass(self, s):
+        """The LDS-sliced scatter-add's prepass (hit bitmaps + compact positions; needs the positions and the live list only).  It
+        used to run on a second stream underneath the MLP backward, but the two share the VALU (87 us overlapped vs 43 alone) and the
+        cross-stream join cost 23 us between the prepass's end and the scatter-add's start: in line it is 17 us per step faster.
+        Returns whether this step's scatter-add is the sliced one (half2 encoder: same prepass, fp16 main pass)."""
+        if self.hash_bwd != "sliced":
+            return False
+        M, A, cfg = s.M, s.A, s.cfg
+        s.ws = A.sliced_ws(cfg.levels)
+        rc = self.L.ngp_hash_bwd_sliced_prep(_ptr(M.xyzs), ctypes.byref(s.lvp), A.cap, _ptr(s.cnt), _ptr(s.live_idx), 1, cfg.lo, cfg.hi,
+                                             _ptr(s.ws), s.ws.numel(), s.st)
+        if rc == -2:
+            # level table not expressible as <= 64 LDS slices per level: the float-atomic kernel from here on.  The overlapped
+            # exchange is built on per-level-group launches of the sliced kernel and shards the optimizer BY GROUP; falling
+            # through to the contiguous shard layout with the group layout still recorded would make state_dict() /
+            # sync_master() gather the wrong ranges (ADVICE r4) -- a trainer configured that way cannot continue
+            if self._groups is not None:
+                raise RuntimeError("NGP_EXPERIMENT comm_overlap=1 needs the LDS-sliced scatter-add, which this level table does not fit "
+                                   "(ngp_hash_bwd_sliced_prep returned -2); unset NGP_EXPERIMENT comm_overlap")
+            self.hash_bwd = "atomic"
+            return False
+        check(rc, "ngp_hash_bwd_sliced_prep")
+        return True
+
+    def _mlp_backward(self, s):
+        """MLP backward over the step's samples -> d_enc.  The weight gradients leave the launch as per-block slabs (plain stores)
+        instead of 256 x 9408 same-address float atomics (13 us of the launch); returns the number of slabs (0: NGP_EXPERIMENT
+        mlp_dw=atomic, round 3's flush straight into mlp_grad, for A/B runs)."""
+        L, M, A = self.L, s.M, s.A
+        head = (_ptr(A.enc), _ptr(M.dirs), _ptr(self.wpack), _ptr(A.d_sigmas), _ptr(A.d_rgbs), A.cap, _ptr(s.cnt), _ptr(s.live_idx),
+                s.P, _ptr(A.d_enc))
+        if self._dw_atomic:
+            check(L.ngp_mlp_bwd_live(*head, _ptr(self.mlp_grad), s.found, s.st), "ngp_mlp_bwd_live")
+            return 0
+        n_parts = L.ngp_mlp_bwd_live_parts(*head, _ptr(self.mlp_parts), s.found, s.st)
+        if n_parts <= 0:
+            check(n_parts or -1, "ngp_mlp_bwd_live_parts")
+        return n_parts
+
+    def _tail_plain(self, s, sliced, n_parts, slabs_to):
+        """Scatter-add -> [gradient exchange] -> prologue -> Adam on the table (+ its 16-bit copy) and the MLP weights + the fp16
+        fragment repack the next step needs (one launch) -> [all-gather of the updated shard]."""
+        L, st, M, A, cfg, found = self.L, s.st, s.M, s.A, s.cfg, s.found
+        if sliced:
+            head = (_ptr(A.d_enc), ctypes.byref(s.lvp), A.cap, _ptr(s.cnt), s.P, _ptr(self.table_grad))
+            if slabs_to == "scatter":
+                check(L.ngp_hash_bwd_sliced_main_slabs(*head, 0, found, _ptr(s.ws), s.ws.numel(), _ptr(self.mlp_parts), n_parts,
+                                                       _ptr(self.mlp_grad), st), "ngp_hash_bwd_sliced_main_slabs")
+            else:
+                name = "ngp_hash_bwd_sliced_main_f16" if self.half else "ngp_hash_bwd_sliced_main"
+                check(getattr(L, name)(*head, found, _ptr(s.ws), s.ws.numel(), st), name)
+        else:
+            name = "ngp_hash_bwd_f16_live" if self.half else "ngp_hash_bwd_f32_live"
+            check(getattr(L, name)(_ptr(M.xyzs), _ptr(A.d_enc), ctypes.byref(cfg.levels), A.cap, _ptr(s.cnt), _ptr(s.live_idx), 1,
+                                   cfg.lo, cfg.hi, s.P, _ptr(self.table_grad), found, st), name)
+        s.pf.reach(4)                                                      # under the gradient exchange + optimizer
         sharded = self.shard and not self._grads_only                      # (gradient diagnostics use the plain all-reduce)
         if sharded:
             self._exchange_sharded(found, st)
@@ -721,90 +748,87 @@ class FusedTrainer:
             if self.half:   # f16 sums overflow easily: GradScaler's check must see the ACCUMULATED (and reduced) gradient
                 check(L.ngp_check_finite_f16(_ptr(self.table_grad), self.table_grad.numel(), found, st), "ngp_check_finite_f16")
         if self._grads_only:
-            return {"rm_samples": total, "vr_per_ray": vr_per_ray, "rgb": rgb, "opacity": opacity, "depth": depth, "rays_a": rays_a,
-                    "deltas": M.deltas, "ts": M.ts, "sq_err": sq_err}
-        if reduce_in_prologue:
-            check(L.ngp_train_prologue_reduce(_ptr(sf), _ptr(si), self.lr0, self.eta_min, self.t_max, self.beta1, self.beta2,
-                                              self.growth, self.backoff, self.growth_interval, _ptr(self.mlp_parts), n_parts,
-                                              _ptr(self.mlp_grad), st), "ngp_train_prologue_reduce")
+            return
+        self._prologue(st, n_parts if slabs_to == "prologue" else 0)
+        if not sharded:
+            self._adam(st, 0, self.nt, self.table_grad)
+            return
+        # Adam on THIS rank's 1/world of the table (its gradient shard is already the cross-rank average); the MLP block of the
+        # launch runs replicated on the all-reduced MLP gradient; then the updated parameters travel back
+        lo = self.rank * self.shard_len
+        self._adam(st, lo, self.shard_len, self.shard_grad)
+        if self.copy16_store is not None:
+            self._all_gather(self.copy16_store, slice(lo, lo + self.shard_len))     # the forward (and the occupancy update) read the 16-bit copy only
+            self._master_stale = True                        # fp32 master of the other ranks' shards: sync_master() on demand
         else:
-            check(L.ngp_train_prologue(_ptr(sf), _ptr(si), self.lr0, self.eta_min, self.t_max, self.beta1,
-                                       self.beta2, self.growth, self.backoff, self.growth_interval, st), "ngp_train_prologue")
-        # Adam on the table (+ its bf16 copy) and on the MLP weights + the fp16 fragment repack the next step needs: one launch
-        kind = 2 if self.half else (1 if self.table_bf16 is not None else 0)
-        if sharded:
-            # Adam on THIS rank's 1/world of the table (its gradient shard is already the cross-rank average); the MLP block of the
-            # launch runs replicated on the all-reduced MLP gradient; then the updated parameters travel back
-            lo = self.rank * self.shard_len
-            sl = slice(lo, lo + self.shard_len)
-            c16 = self.copy16_store[sl] if self.copy16_store is not None else None
-            check(L.ngp_adam_all_ex(_ptr(self.table_store[sl]), _ptr(self.shard_grad), int(self.half), _ptr(self.table_m[sl]),
-                                    _ptr(self.table_v[sl]), self.shard_len, _ptr(c16), kind, _ptr(self.mlp_flat), _ptr(self.mlp_grad),
-                                    _ptr(self.mlp_m), _ptr(self.mlp_v), _ptr(sf), _ptr(si), self.beta1, self.beta2, self.eps, P,
-                                    _ptr(self.wpack), st), "ngp_adam_all_ex")
-            if self.copy16_store is not None:
-                self._all_gather(self.copy16_store, sl)          # the forward (and the occupancy update) read the 16-bit copy only
-                self._master_stale = True                        # fp32 master of the other ranks' shards: sync_master() on demand
-            else:
-                self._all_gather(self.table_store, sl)
-        else:
-            copy16 = self.copy16_store[:self.nt] if self.copy16_store is not None else None
-            check(L.ngp_adam_all_ex(_ptr(self.table), _ptr(self.table_grad), int(self.half), _ptr(self.table_m), _ptr(self.table_v),
-                                    self.table.numel(), _ptr(copy16), kind, _ptr(self.mlp_flat), _ptr(self.mlp_grad), _ptr(self.mlp_m),
-                                    _ptr(self.mlp_v), _ptr(sf), _ptr(si), self.beta1, self.beta2, self.eps, P, _ptr(self.wpack), st),
-                  "ngp_adam_all_ex")
-        return {"rm_samples": total, "vr_per_ray": vr_per_ray, "rgb": rgb, "opacity": opacity, "depth": depth, "rays_a": rays_a,
-                "deltas": M.deltas, "ts": M.ts, "sq_err": sq_err}
+            self._all_gather(self.table_store, slice(lo, lo + self.shard_len))
 
-    def _shade_all(self, M, cfg, A, P, st, total, hook):
-        """Encode + MLP forward over every marched sample (reference networks.py:136-166 on all of raymarching_train's output)."""
+    def _prologue(self, st, n_parts=0):
+        """The step's scalar bookkeeping on the device (inf check -> loss-scale growth / backoff, learning rate, bias corrections);
+        with n_parts the same launch sums the MLP backward's weight-gradient slabs first."""
+        L, sf, si = self.L, self.state_f, self.state_i
+        hyper = (self.lr0, self.eta_min, self.t_max, self.beta1, self.beta2, self.growth, self.backoff, self.growth_interval)
+        if n_parts:
+            check(L.ngp_train_prologue_reduce(_ptr(sf), _ptr(si), *hyper, _ptr(self.mlp_parts), n_parts, _ptr(self.mlp_grad), st),
+                  "ngp_train_prologue_reduce")
+        else:
+            check(L.ngp_train_prologue(_ptr(sf), _ptr(si), *hyper, st), "ngp_train_prologue")
+
+    def _adam(self, st, lo, n, grad, mlp=True):
+        """Adam on table_store[lo:lo + n] (moments and 16-bit copy at the same offset) with gradient `grad`, and -- with mlp -- on the
+        MLP weights + the fp16 fragment repack, in one launch; n = 0: the MLP block alone."""
         L = self.L
-        if self.half:
-            check(L.ngp_hash_fwd_f16_ex(_ptr(M.xyzs), _ptr(self.table_f16), ctypes.byref(cfg.levels), A.cap, _ptr(total), 1, cfg.lo,
-                                        cfg.hi, P, _ptr(A.enc), st), "ngp_hash_fwd_f16_ex")
-        elif self.table_bf16 is not None:
-            check(L.ngp_hash_fwd_bf16_ex(_ptr(M.xyzs), _ptr(self.table_bf16), ctypes.byref(cfg.levels), A.cap, _ptr(total), 1, cfg.lo,
-                                         cfg.hi, P, _ptr(A.enc), st), "ngp_hash_fwd_bf16_ex")
-        else:
-            check(L.ngp_hash_fwd_f32_ex(_ptr(M.xyzs), _ptr(self.table), ctypes.byref(cfg.levels), A.cap, _ptr(total), 1, cfg.lo,
-                                        cfg.hi, P, _ptr(A.enc), st), "ngp_hash_fwd_f32_ex")
-        if hook is not None and self._hook_at == 1:
-            hook(); hook = None
-        check(L.ngp_mlp_fwd_ex(_ptr(A.enc), _ptr(M.dirs), _ptr(self.wpack), A.cap, _ptr(total), P, _ptr(A.sigmas), _ptr(A.rgbs), st),
-              "ngp_mlp_fwd_ex")
-        if hook is not None and self._hook_at == 2:
-            hook(); hook = None
-        return hook
+        quartet = [_ptr(t if mlp else None) for t in (self.mlp_flat, self.mlp_grad, self.mlp_m, self.mlp_v)]
+        rest = (_ptr(self.state_f), _ptr(self.state_i), self.beta1, self.beta2, self.eps, self.enc_pairs, _ptr(self.wpack), st)
+        if n == 0:
+            check(L.ngp_adam_mlp_pack(*quartet, *rest), "ngp_adam_mlp_pack")
+            return
 
-    def _shade_chunked(self, M, n, cfg, A, P, st, hook):
+        def at(t):
+            return ctypes.c_void_p(t.data_ptr() + lo * t.element_size()) if t is not None else ctypes.c_void_p(0)
+        check(L.ngp_adam_all_ex(at(self.table_store), _ptr(grad), int(self.half), at(self.table_m), at(self.table_v), n,
+                                at(self.copy16_store), self._kind16, *quartet, *rest), "ngp_adam_all_ex")
+
+    _GATHER = ("ngp_hash_fwd_f32_ex", "ngp_hash_fwd_bf16_ex", "ngp_hash_fwd_f16_ex")     # by the storage kind of the table the forward reads
+
+    def _forward_all(self, s):
+        """Encode + MLP forward over every marched sample (reference networks.py:136-166 on all of raymarching_train's output)."""
+        L, M, A, cfg, st = self.L, s.M, s.A, s.cfg, s.st
+        name = self._GATHER[self._kind16]
+        check(getattr(L, name)(_ptr(M.xyzs), _ptr(self._fwd_table), ctypes.byref(cfg.levels), A.cap, _ptr(M.total), 1, cfg.lo, cfg.hi,
+                               s.P, _ptr(A.enc), st), name)
+        s.pf.reach(1)
+        check(L.ngp_mlp_fwd_ex(_ptr(A.enc), _ptr(M.dirs), _ptr(self.wpack), A.cap, _ptr(M.total), s.P, _ptr(A.sigmas), _ptr(A.rgbs), st),
+              "ngp_mlp_fwd_ex")
+        s.pf.reach(2)
+
+    def _forward_chunked(self, s):
         """Encode + MLP forward in rounds over the samples compositing can still reach (see __init__; csrc/composite.hip
         chunk_schedule_kernel).  Returns False when the level table does not fit the list encoder (the caller shades everything)."""
-        L = self.L
+        L, M, A, cfg, st, n, P = self.L, s.M, s.A, s.cfg, s.st, s.n, s.P
         R = len(self._chunk_rounds)
         T_state = self._chunk_state(n)
         par = M.index
         c_cur = self._chunk_counts.data_ptr() + 4 * R * par             # this step's list lengths; the other parity's set is cleared
         c_oth = self._chunk_counts.data_ptr() + 4 * R * (1 - par)       # round by round for the next step
-        table, kind = (self.table_bf16, 1) if self.table_bf16 is not None else (self.table, 0)
         lst = A.live_idx                    # (free until the composite kernel writes the backward's live list into it)
         for r, (b, l, pb) in enumerate(self._chunk_rounds):
             cnt = ctypes.c_void_p(c_cur + 4 * r)
             check(L.ngp_chunk_schedule(_ptr(M.rays_a), _ptr(A.sigmas), _ptr(M.deltas), n, b, l, pb, 0.5 * cfg.T_threshold, _ptr(T_state),
                                        _ptr(lst), cnt, ctypes.c_void_p(c_oth + 4 * r), st), "ngp_chunk_schedule")
-            rc = L.ngp_hash_fwd_list(_ptr(M.xyzs), _ptr(table), kind, ctypes.byref(cfg.levels), A.cap, cnt, _ptr(lst), 1,
+            rc = L.ngp_hash_fwd_list(_ptr(M.xyzs), _ptr(self._fwd_table), self._kind16, ctypes.byref(cfg.levels), A.cap, cnt, _ptr(lst), 1,
                                      cfg.lo, cfg.hi, P, _ptr(A.enc), st)
             if rc == -2 and r == 0:                                        # level table outside the list encoder: shade everything
                 self._chunk_counts.zero_()
                 self.chunked = False
-                return False, hook
+                return False
             check(rc, "ngp_hash_fwd_list")
-            if r == 0 and hook is not None and self._hook_at == 1:
-                hook(); hook = None
+            if r == 0:
+                s.pf.reach(1)
             check(L.ngp_mlp_fwd_list(_ptr(A.enc), _ptr(M.dirs), _ptr(self.wpack), A.cap, cnt, _ptr(lst), P, _ptr(A.sigmas),
                                      _ptr(A.rgbs), st), "ngp_mlp_fwd_list")
-        if hook is not None and self._hook_at == 2:
-            hook(); hook = None
-        return True, hook
+        s.pf.reach(2)
+        return True
 
     def _chunk_state(self, n):
         """Buffers of the chunked forward for n rays per step: [2, rounds] list counters (one set per step parity, all zero between
@@ -822,45 +846,31 @@ class FusedTrainer:
             return None
         return int(self._chunk_counts[1 - self._cur].sum())
 
-    def _tail_flush_adam(self, A, M, cfg, cnt, P, ws, n_parts, st, hook, total, vr_per_ray, rgb, opacity, depth, sq_err, npre):
-        """Prologue -> scatter-add with the optimizer in its flush -> Adam on the replicated coarse levels + the MLP (one GPU, fp32
-        master table with or without the bf16 copy; see __init__)."""
-        L, sf, si, lvp = self.L, self.state_f, self.state_i, self._lvp
-        copy16 = self.copy16_store[:self.nt] if self.copy16_store is not None else None
+    def _tail_flush_adam(self, s, n_parts, npre):
+        """Prologue -> scatter-add with the optimizer in its flush -> Adam on the replicated coarse levels [0, npre) + the MLP (one
+        GPU, fp32 master table with or without the bf16 copy; see __init__)."""
+        L, A, st, sf, si = self.L, s.A, s.st, self.state_f, self.state_i
+        args = (_ptr(A.d_enc), ctypes.byref(s.lvp), A.cap, _ptr(s.cnt), s.P, _ptr(self.table_grad), _ptr(s.ws), s.ws.numel(),
+                _ptr(self.mlp_parts), n_parts, _ptr(self.mlp_grad), _ptr(self.table), _ptr(self.table_m), _ptr(self.table_v),
+                _ptr(self._copy16), _ptr(sf), _ptr(si))
         if self._fold_prologue:
             # the GradScaler / schedule decision is evaluated inside the scatter-add launch (no one-thread launch in front of it)
-            check(L.ngp_hash_bwd_sliced_main_adam_step(_ptr(A.d_enc), ctypes.byref(lvp), A.cap, _ptr(cnt), P, _ptr(self.table_grad),
-                                                       _ptr(ws), ws.numel(), _ptr(self.mlp_parts), n_parts, _ptr(self.mlp_grad),
-                                                       _ptr(self.table), _ptr(self.table_m), _ptr(self.table_v), _ptr(copy16), _ptr(sf),
-                                                       _ptr(si), self.lr0, self.eta_min, self.t_max, self.beta1, self.beta2, self.eps,
+            check(L.ngp_hash_bwd_sliced_main_adam_step(*args, self.lr0, self.eta_min, self.t_max, self.beta1, self.beta2, self.eps,
                                                        self.growth, self.backoff, self.growth_interval, st),
                   "ngp_hash_bwd_sliced_main_adam_step")
         else:
-            check(L.ngp_train_prologue(_ptr(sf), _ptr(si), self.lr0, self.eta_min, self.t_max, self.beta1, self.beta2, self.growth,
-                                       self.backoff, self.growth_interval, st), "ngp_train_prologue")
-            check(L.ngp_hash_bwd_sliced_main_adam(_ptr(A.d_enc), ctypes.byref(lvp), A.cap, _ptr(cnt), P, _ptr(self.table_grad), _ptr(ws),
-                                                  ws.numel(), _ptr(self.mlp_parts), n_parts, _ptr(self.mlp_grad), _ptr(self.table),
-                                                  _ptr(self.table_m), _ptr(self.table_v), _ptr(copy16), _ptr(sf), _ptr(si), self.beta1,
-                                                  self.beta2, self.eps, st), "ngp_hash_bwd_sliced_main_adam")
-        if hook is not None:
-            hook()                                                          # position 4
-        kind = 1 if copy16 is not None else 0
-        if npre > 0:
-            check(L.ngp_adam_all_ex(_ptr(self.table), _ptr(self.table_grad), 0, _ptr(self.table_m), _ptr(self.table_v), npre,
-                                    _ptr(copy16), kind, _ptr(self.mlp_flat), _ptr(self.mlp_grad), _ptr(self.mlp_m), _ptr(self.mlp_v),
-                                    _ptr(sf), _ptr(si), self.beta1, self.beta2, self.eps, P, _ptr(self.wpack), st), "ngp_adam_all_ex")
-        else:
-            check(L.ngp_adam_mlp_pack(_ptr(self.mlp_flat), _ptr(self.mlp_grad), _ptr(self.mlp_m), _ptr(self.mlp_v), _ptr(sf), _ptr(si),
-                                      self.beta1, self.beta2, self.eps, P, _ptr(self.wpack), st), "ngp_adam_mlp_pack")
-        return {"rm_samples": total, "vr_per_ray": vr_per_ray, "rgb": rgb, "opacity": opacity, "depth": depth, "rays_a": M.rays_a,
-                "deltas": M.deltas, "ts": M.ts, "sq_err": sq_err}
+            self._prologue(st)
+            check(L.ngp_hash_bwd_sliced_main_adam(*args, self.beta1, self.beta2, self.eps, st), "ngp_hash_bwd_sliced_main_adam")
+        s.pf.reach(4)
+        self._adam(st, 0, npre, self.table_grad)
 
-    def _composite_with_distortion(self, A, M, target, cfg, n, vr_per_ray, opacity, depth, rgb):
+    def _composite_with_distortion(self, s, target):
         """loss = MSE + w * mean(distortion) (train.py:193-195): the distortion gradient w.r.t. the sample weights has to
         exist before the composite backward runs, so the single fused launch becomes composite fwd -> distortion fwd/bwd ->
-        MSE gradient -> composite bwd (all the same kernels the operator path uses).  Returns the per-ray squared error
+        MSE gradient -> composite bwd (all the same kernels the operator path uses).  s.sq_err becomes the per-ray squared error
         stand-in used for logging (MSE part only)."""
-        L, st, sf = self.L, _stream(), self.state_f
+        L, st, sf = self.L, s.st, self.state_f
+        A, M, cfg, n, vr_per_ray, opacity, depth, rgb = s.A, s.M, s.cfg, s.n, s.vr_per_ray, s.opacity, s.depth, s.rgb
         f32 = dict(device=self.dev, dtype=torch.float32)
         rays_a = M.rays_a
         check(L.ngp_composite_train_fwd(_ptr(A.sigmas), _ptr(A.rgbs), 1, _ptr(M.deltas), _ptr(M.ts), _ptr(rays_a), cfg.T_threshold,
@@ -882,11 +892,7 @@ class FusedTrainer:
                                         _ptr(M.ts), _ptr(rays_a), _ptr(opacity), _ptr(depth), _ptr(rgb), _ptr(A.ws), cfg.T_threshold, n,
                                         _ptr(A.d_sigmas), _ptr(A.d_rgbs), st), "ngp_composite_train_bwd")
         self._dist_loss = dist_loss
-        return sq_err
-
-    # ---- world > 1, sharded optimizer: reduce-scatter -> Adam on the own shard -> all-gather ------------------------------
-    def _nccl(self):
-        return dist.get_backend(self.group) == "nccl"
+        s.sq_err = sq_err
 
     # ---- overlapped exchange: one launch + one reduce-scatter / Adam / all-gather per level group (ngp_hip/dist.py) ------------
     def _make_groups(self, lvs, spec):
@@ -907,10 +913,6 @@ class FusedTrainer:
         self._gx.stub = self._comm_stub
         return self._gx.ag_async(g, store)
 
-    def _timed_wait(self, name, fn):
-        """Overlapped exchange: what the step's stream WAITS for a collective that was issued earlier (sampled steps only)."""
-        return self._timed(name, fn)
-
     def finish_comm(self):
         """Overlapped exchange: make the step's stream wait for the all-gathers of the previous step (before anything reads the
         table: the next forward, an occupancy update, a checkpoint)."""
@@ -923,58 +925,53 @@ class FusedTrainer:
         for g in self._groups:
             self._ag_async(g, store)()
 
-    def _tail_overlapped(self, A, cfg, cnt, P, ws, found, st, hook, reduce_parts):
+    def _tail_overlapped(self, s):
         """Scatter-add, gradient exchange and optimizer of one step with the exchange overlapped (see __init__)."""
-        L, sf, si, lvp = self.L, self.state_f, self.state_i, self._lvp
+        L, A, st = self.L, s.A, s.st
         max_blocks = int(_exp.get("comm_scatter_blocks", "240"))     # leave CUs for RCCL's workgroups beside the later launches
         fins = []
         for k, g in enumerate(self._groups):
-            check(L.ngp_hash_bwd_sliced_main_levels(_ptr(A.d_enc), ctypes.byref(lvp), A.cap, _ptr(cnt), P, _ptr(self.table_grad),
-                                                    found, _ptr(ws), ws.numel(), g.mask, 0 if k == 0 else max_blocks, st),
+            check(L.ngp_hash_bwd_sliced_main_levels(_ptr(A.d_enc), ctypes.byref(s.lvp), A.cap, _ptr(s.cnt), s.P, _ptr(self.table_grad),
+                                                    s.found, _ptr(s.ws), s.ws.numel(), g.mask, 0 if k == 0 else max_blocks, st),
                   "ngp_hash_bwd_sliced_main_levels")
             fins.append(self._rs_async(g))
-        if hook is not None:
-            hook()                                                          # the next batch's march: under the exchange
-        # [MLP gradient | inf flag]: every rank has to take the same skip / step decision; behind the last reduce-scatter
-        flag_i = si[_SI_FOUND_INF:_SI_FOUND_INF + 1]
-        self._flag_f.copy_(flag_i)
-        small_work = None
-        if not self._comm_stub:
-            if self._nccl():
-                small_work = dist.all_reduce(self.small_bucket, op=dist.ReduceOp.AVG, group=self.group, async_op=True)
-            else:
-                small_work = dist.all_reduce(self.small_bucket, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
-        def wait_small():
-            if small_work is not None:
-                small_work.wait()
-        self._timed_wait("wait_all_reduce_mlp_grad_and_flag", wait_small)
-        if small_work is not None and not self._nccl():
-            self.small_bucket.div_(self.world)
-        flag_i.copy_(self._flag_f != 0)
-        self._flag_f.zero_()
-        check(L.ngp_train_prologue(_ptr(sf), _ptr(si), self.lr0, self.eta_min, self.t_max, self.beta1, self.beta2, self.growth,
-                                   self.backoff, self.growth_interval, st), "ngp_train_prologue")
-        kind = 1 if self.table_bf16 is not None else 0
+        s.pf.reach(4)                                                       # the next batch's march: under the exchange
+
+        def small():      # [MLP gradient | inf flag], behind the last reduce-scatter; what the step's stream WAITS for it is timed
+            self._timed("wait_all_reduce_mlp_grad_and_flag", self._rank_avg(self.small_bucket, async_op=True))
+        self._carry_flag(small)
+        self._prologue(st)
         back = self.copy16_store if self.copy16_store is not None else self.table_store
         for k, (g, fin) in enumerate(zip(self._groups, fins)):
             fin()                                                           # this group's averaged gradient chunk has arrived
-            n_own = g.hi - g.lo
-            if n_own > 0:
-                sl = slice(g.lo, g.hi)
-                c16 = self.copy16_store[sl] if self.copy16_store is not None else None
-                mlp = (self.mlp_flat, self.mlp_grad, self.mlp_m, self.mlp_v) if k == 0 else (None, None, None, None)
-                check(L.ngp_adam_all_ex(_ptr(self.table_store[sl]), _ptr(g.shard), 0, _ptr(self.table_m[sl]), _ptr(self.table_v[sl]),
-                                        n_own, _ptr(c16), kind, _ptr(mlp[0]), _ptr(mlp[1]), _ptr(mlp[2]), _ptr(mlp[3]), _ptr(sf),
-                                        _ptr(si), self.beta1, self.beta2, self.eps, P, _ptr(self.wpack), st), "ngp_adam_all_ex")
+            if g.hi > g.lo:
+                self._adam(st, g.lo, g.hi - g.lo, g.shard, mlp=k == 0)
             self._pending_comm.append(self._ag_async(g, back))
         if self.copy16_store is not None:
             self._master_stale = True
 
+    # ---- world > 1: the rank average, the inf flag that rides along, and the sharded optimizer's exchange ----------------------
+    def _rank_avg(self, t, async_op=False):
+        """t <- mean over the ranks (dist.all_reduce_avg); NGP_EXPERIMENT comm_stub: its local part, which is t.  async_op: starts
+        it and returns finish()."""
+        if self._comm_stub:
+            return (lambda: None) if async_op else None
+        return all_reduce_avg(t, self.world, self.group, async_op)
+
+    def _carry_flag(self, collective):
+        """Run collective() with the inf flag riding in the bucket as a float (_flag_f, the last element of small_bucket / grad_flat):
+        every rank has to take the same skip / step decision, and any rank's non-zero flag leaves a non-zero sum / mean."""
+        flag_i = self.state_i[_SI_FOUND_INF:_SI_FOUND_INF + 1]
+        self._flag_f.copy_(flag_i)
+        collective()
+        flag_i.copy_(self._flag_f != 0)
+        self._flag_f.zero_()
+
     def _exchange_sharded(self, found, st):
         """(1) reduce-scatter of the padded table gradient: this rank receives the cross-rank AVERAGE of shard `rank` (MSE is a
         mean over the local ray shard); the local accumulator is cleared for the next step.  (2) one small all-reduce of
-        [MLP gradient | inf flag] (37.6 KB): the MLP Adam runs replicated, and every rank has to take the same skip / step
-        decision (the half2 encoder's f16 gradient shard is scanned for inf first: f16 sums overflow)."""
+        [MLP gradient | inf flag] (37.6 KB): the MLP Adam runs replicated (the half2 encoder's f16 gradient shard is scanned for
+        inf first: f16 sums overflow)."""
         src = self.table_grad_store
         if self._comm is not None:                                 # 16-bit transport of the fp32 gradient (bench.py --comm bf16)
             self._comm.copy_(src)
@@ -985,19 +982,7 @@ class FusedTrainer:
         src.zero_()
         if self.half:
             check(self.L.ngp_check_finite_f16(_ptr(self.shard_grad), self.shard_grad.numel(), found, st), "ngp_check_finite_f16")
-        flag_i = self.state_i[_SI_FOUND_INF:_SI_FOUND_INF + 1]
-        self._flag_f.copy_(flag_i)
-        def small():
-            if self._comm_stub:
-                return
-            if self._nccl():
-                dist.all_reduce(self.small_bucket, op=dist.ReduceOp.AVG, group=self.group)
-            else:
-                dist.all_reduce(self.small_bucket, op=dist.ReduceOp.SUM, group=self.group)
-                self.small_bucket.div_(self.world)
-        self._timed("all_reduce_mlp_grad_and_flag", small)
-        flag_i.copy_(self._flag_f != 0)
-        self._flag_f.zero_()
+        self._carry_flag(lambda: self._timed("all_reduce_mlp_grad_and_flag", lambda: self._rank_avg(self.small_bucket)))
 
     def _timed(self, name, fn):
         """Run one collective; with a bench probe attached, bracket it with HIP events on the current stream (a synchronous
@@ -1060,33 +1045,18 @@ class FusedTrainer:
 
     def _all_reduce(self):
         """Average the gradients of the ray shards (MSE is a mean over the local shard) and OR the inf flags: ONE
-        collective over the flat bucket [table grad | MLP grad | flag] (the flag rides along as a float; any rank's
-        non-zero flag leaves a non-zero sum / mean)."""
-        flag_i = self.state_i[_SI_FOUND_INF:_SI_FOUND_INF + 1]
-        self._flag_f.copy_(flag_i)
-        if self.half:                                              # the f16 table gradient travels as it is (22.8 MB)
-            if dist.get_backend(self.group) == "nccl":
-                dist.all_reduce(self.table_grad, op=dist.ReduceOp.AVG, group=self.group)
-            else:
-                dist.all_reduce(self.table_grad, op=dist.ReduceOp.SUM, group=self.group)
-                self.table_grad.div_(self.world)
-        buf = self.grad_flat
-        if self._comm is not None and not self.shard:
-            buf = self._comm
-            buf.copy_(self.grad_flat)                           # loss-scaled gradients: bf16 keeps the fp32 exponent range
-        def flat():
-            if self._comm_stub:
-                return
-            if dist.get_backend(self.group) == "nccl":
-                dist.all_reduce(buf, op=dist.ReduceOp.AVG, group=self.group)
-            else:
-                dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
-                buf.div_(self.world)
-        self._timed("all_reduce_flat_bucket", flat)
-        if buf is not self.grad_flat:
-            self.grad_flat.copy_(buf)
-        flag_i.copy_(self._flag_f != 0)
-        self._flag_f.zero_()
+        collective over the flat bucket [table grad | MLP grad | flag]."""
+        def bucket():
+            if self.half:                                              # the f16 table gradient travels as it is (22.8 MB)
+                all_reduce_avg(self.table_grad, self.world, self.group)
+            buf = self.grad_flat
+            if self._comm is not None and not self.shard:
+                buf = self._comm
+                buf.copy_(self.grad_flat)                           # loss-scaled gradients: bf16 keeps the fp32 exponent range
+            self._timed("all_reduce_flat_bucket", lambda: self._rank_avg(buf))
+            if buf is not self.grad_flat:
+                self.grad_flat.copy_(buf)
+        self._carry_flag(bucket)
 
     def step(self, rays_o, rays_d, target, prefetch=None, noise=None):
         """rays_o, rays_d, target: [N,3] contiguous float32 device tensors (this rank's shard).  Returns the per-step

@@ -215,3 +215,36 @@ def test_grouped_exchange_three_ranks_bf16_transport_cpu(tmp_path):
     world = 3
     mp.spawn(_grouped_worker, args=(world, _free_port(), "4,0", True, str(tmp_path)), nprocs=world, join=True)
     assert sorted(os.listdir(tmp_path)) == ["ok_%d" % r for r in range(world)]
+
+
+# ---- the one rank average (ngp_hip/dist.py: all_reduce_avg) and its users -----------------------------------------------------
+def _avg_worker(rank, world, port, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "taichi-nerfs_amd"))
+    from ngp_hip.dist import GradReducer, all_reduce_avg
+    g = torch.Generator().manual_seed(7)
+    vals = torch.randn(world, 1000, generator=g)                           # rank r holds vals[r]
+    want = vals.sum(0) / world                                               # what SUM followed by a division by world gives, bit for bit
+    t = vals[rank].clone()
+    assert all_reduce_avg(t, world) is None and torch.equal(t, want)         # synchronous: done on return
+    t = vals[rank].clone()
+    finish = all_reduce_avg(t, world, async_op=True)
+    finish()
+    assert torch.equal(t, want)                                              # through finish(): waits, then divides -- once
+    # GradReducer: the big tensor by its own collective, the small ones as one flat bucket -- each the same mean
+    big, small = torch.nn.Parameter(torch.zeros(1 << 12)), torch.nn.Parameter(torch.zeros(10, 100))
+    big.grad, small.grad = vals[rank].repeat(5)[:1 << 12].clone(), vals[rank].view(10, 100).clone()
+    mod = torch.nn.ParameterList([big, small])
+    GradReducer(mod, world, big_numel=1 << 12).all_reduce()
+    assert torch.equal(big.grad, want.repeat(5)[:1 << 12]) and torch.equal(small.grad, want.view(10, 100))
+    open(os.path.join(out_dir, "ok_%d" % rank), "w").write("ok")
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_all_reduce_avg_is_the_mean_sync_and_async_two_ranks(tmp_path):
+    world = 2
+    mp.spawn(_avg_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    assert sorted(os.listdir(tmp_path)) == ["ok_%d" % r for r in range(world)]

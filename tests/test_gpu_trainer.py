@@ -565,6 +565,44 @@ def test_prefetched_march_placement_adapts_to_the_march_it_follows(hip_lib, lego
     assert not tr2._adaptive_prefetch and tr2._prefetch_at == 2 and tr2._marched_host is None
 
 
+_PREFETCH_AT_REF = {}                  # chunked -> what position 3 ends with (computed once)
+
+
+def _run_prefetch_at(lego_bitfield, pos, chunked):
+    from ngp_hip.trainer import FusedTrainer
+    n = 1024
+    m, o, d, target = _make(lego_bitfield, n=n)
+    tr = FusedTrainer(m, init_scale=2.0**10, max_samples=256, chunked_forward=chunked).set_deterministic(True)
+    assert tr.chunked == chunked and len(tr._chunk_rounds) == (3 if chunked else 0)
+    tr._adaptive_prefetch, tr._prefetch_at = False, pos
+    torch.manual_seed(5)                       # the jitter seeds come from torch's CPU generator, one per march
+    hits0 = tr.prefetch_hits
+    for _ in range(4):
+        tr.step(o, d, target, prefetch=(o, d))
+    torch.cuda.synchronize()
+    out = ([t.clone().view(torch.int32) for t in (tr.table, tr.mlp_flat, tr.state_i)], tr.prefetch_hits - hits0, tr._hook_at)
+    tr.close()
+    return out
+
+
+@pytest.mark.parametrize("chunked", [False, True], ids=["all", "chunked"])
+@pytest.mark.parametrize("pos", [0, 1, 2, 2.5, 2.75, 3, 4])
+def test_prefetch_position_does_not_change_the_result(hip_lib, lego_bitfield, monkeypatch, pos, chunked):
+    """The next batch's march is issued at one of seven positions of the step (trainer._prefetch_at; ngp_hip/trainer.py
+    _PrefetchPoint).  It reads the rays and the bitfield only, so where it is issued changes nothing: in deterministic mode four
+    prefetched steps end with the same bytes in the table, the MLP weights and the step counters as at position 3, and the last
+    three steps each consume the march the step before issued -- with the forward over every sample and chunked (three rounds)."""
+    monkeypatch.delenv("NGP_EXPERIMENT", raising=False)
+    if chunked not in _PREFETCH_AT_REF:
+        _PREFETCH_AT_REF[chunked] = _run_prefetch_at(lego_bitfield, 3, chunked)
+    ref, ref_hits, ref_at = _PREFETCH_AT_REF[chunked]
+    assert ref_hits == 3 and ref_at == 3
+    got, hits, at = _run_prefetch_at(lego_bitfield, pos, chunked)
+    assert hits == 3 and at == pos
+    for name, a, b in zip(("table", "mlp_flat", "state_i"), got, ref):
+        assert torch.equal(a, b), name
+
+
 def test_host_side_wait_for_the_prefetched_march_changes_nothing(hip_lib, lego_bitfield, monkeypatch):
     """Round 6, opt-in (NGP_EXPERIMENT prefetch_host_wait=1): where the next batch's march was issued at the START of the previous step, the
     HOST waits for its event (ngp_event_synchronize) instead of the main stream (a satisfied cross-queue event wait costs it ~10 us).  Same
