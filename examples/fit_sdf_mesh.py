@@ -31,6 +31,34 @@ def torus_sdf(x, R=0.25, r=0.1):
     return torch.sqrt((torch.linalg.norm(x[:, :2], dim=1) - R) ** 2 + x[:, 2] ** 2) - r
 
 
+def fit(field, target_sdf, steps, n, sigma, uniform_fraction, lr, eikonal_weight, gen):
+    """The fitting loop (examples/render_mesh.py runs it too): `steps` Adam steps of |f - sdf_mesh| + eikonal_weight (|grad f| - 1)^2 on
+    the points target_sdf.sample draws from `gen` -> ([(sdf loss, eikonal error) of the first and the last step], the summed time of the
+    distance queries in ms)."""
+    opt = torch.optim.Adam(field.geo_layers.parameters(), lr=lr, eps=1e-15)
+    opt.add_param_group({"params": field.pos_encoder.parameters()})
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    hist, query_ms = [], 0.0
+    for step in range(steps):
+        x = target_sdf.sample(n, sigma, uniform_fraction, gen).clamp_(-0.5, 0.5)
+        t0.record()
+        d = target_sdf(x, details=False).sdf
+        t1.record()
+        f, _, grad = field.sdf_and_grad(x.requires_grad_(), create_graph=True)
+        norm = torch.linalg.norm(grad, dim=1)
+        sdf_loss = (f - d).abs().mean()
+        loss = sdf_loss + eikonal_weight * ((norm - 1.0) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        t1.synchronize()
+        query_ms += t0.elapsed_time(t1)
+        if step in (0, steps - 1):
+            hist.append((float(sdf_loss.detach()), float((norm.detach() - 1.0).abs().mean())))
+    torch.cuda.synchronize()
+    return hist, query_ms
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=1000)
@@ -69,28 +97,8 @@ def main(argv=None):
         return {"mean_cells": sd["mean"] / cell, "max_cells": sd["max"] / cell}
 
     untrained = compare(extract())
-    opt = torch.optim.Adam(field.geo_layers.parameters(), lr=args.lr, eps=1e-15)
-    opt.add_param_group({"params": field.pos_encoder.parameters()})
-    gen = torch.Generator().manual_seed(args.seed)
-    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    hist, query_ms = [], 0.0
-    for step in range(args.steps):
-        x = target_sdf.sample(args.n, args.sigma, args.uniform_fraction, gen).clamp_(-0.5, 0.5)
-        t0.record()
-        d = target_sdf(x, details=False).sdf
-        t1.record()
-        f, _, grad = field.sdf_and_grad(x.requires_grad_(), create_graph=True)
-        norm = torch.linalg.norm(grad, dim=1)
-        sdf_loss = (f - d).abs().mean()
-        loss = sdf_loss + args.eikonal_weight * ((norm - 1.0) ** 2).mean()
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        opt.step()
-        t1.synchronize()
-        query_ms += t0.elapsed_time(t1)
-        if step in (0, args.steps - 1):
-            hist.append((float(sdf_loss.detach()), float((norm.detach() - 1.0).abs().mean())))
-    torch.cuda.synchronize()
+    hist, query_ms = fit(field, target_sdf, args.steps, args.n, args.sigma, args.uniform_fraction, args.lr, args.eikonal_weight,
+                         torch.Generator().manual_seed(args.seed))
     result = extract()
     info = {"steps": args.steps, "points_per_step": args.n, "levels": args.levels, "log2_T": args.log2_T, "max_res": args.max_res,
             "target_resolution": args.target_resolution, "resolution": args.resolution, "target_faces": int(target.faces.shape[0]),

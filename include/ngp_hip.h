@@ -740,6 +740,29 @@ int ngp_mesh_sdf_query(const float* points, int n, const float* vertices, const 
                        float* sdf, float* closest /* may be NULL */, int32_t* face /* may be NULL */, int32_t* feature /* may be NULL */,
                        void* stream);
 
+/* ---- ray casting against a triangle mesh: the first face along a ray, in the same hierarchy (csrc/mesh_raycast.hip)
+ * vertices, faces, order, boxes, n_faces, leaf_size: the tree ngp_mesh_bvh_build made, read only.  rays_o, rays_d f32 [n,3]; directions
+ * need not be normalised.  One launch, one lane per ray.  Per ray the face that minimises t in [t_min, t_max] by the watertight test of
+ * Woop, Benthin & Wald 2013 in f32 (the formula in csrc/mesh_raycast.hip): no ray slips between two faces that share an edge or a vertex.
+ * t [n]    : the ray parameter in units of |d| (the hit point is o + t d); +inf on a miss
+ * face [n] : a row of `faces` (the caller's numbering); -1 on a miss
+ * bary [n,2] : (v, w), the hit point is a + v (b - a) + w (c - a), the convention of sdf_query's closest point; 0 on a miss
+ * side [n] : +1 the front of the face was hit (d . cross(b - a, c - a) < 0, by the sign of the determinant), -1 the back, 0 a miss
+ * face, bary, side may be NULL; t has the same bits with or without them.  flags: NGP_RAYCAST_ANY_HIT stops at the first accepted face (the
+ * occlusion query: t and face are then those of AN accepted face), NGP_RAYCAST_CULL_BACK / NGP_RAYCAST_CULL_FRONT skip back- / front-
+ * facing faces.  A face without area is never hit.  A ray with a zero or non-finite direction, a NaN anywhere, or t_min <= t_max false
+ * is a miss; the walk ends after a bounded number of steps for any bit pattern.  A result depends on its ray and the mesh alone.
+ * Returns -1 without a launch for a null required pointer, a size bvh_bytes refuses, n < 0 or unknown flag bits; 0 without a launch for
+ * n = 0 (rays_o, rays_d and t may then be null). */
+#define NGP_RAYCAST_ANY_HIT 1
+#define NGP_RAYCAST_CULL_BACK 2
+#define NGP_RAYCAST_CULL_FRONT 4
+int ngp_mesh_raycast(const float* rays_o, const float* rays_d, int n,
+                     const float* vertices, const int32_t* faces, const int32_t* order, const float* boxes,
+                     int n_faces, int leaf_size, float t_min, float t_max, int flags,
+                     float* t /*[n]*/, int32_t* face /*[n], may be NULL*/, float* bary /*[n,2], may be NULL*/,
+                     int32_t* side /*[n], may be NULL*/, void* stream);
+
 /* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
  * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
  * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],

@@ -51,35 +51,14 @@
 // THE SIGN (signed mode: both normal arrays given): s = +1 if n.r >= 0 else -1, n by the feature of the winning face f -- interior:
 // cross(ab, ac), unnormalised; edge e: edge_normals[f, e]; vertex k: vertex_normals[faces[f, k]] (the angle-weighted pseudonormals of
 // Baerentzen & Aanaes 2005, made by the caller).  sdf = s sqrt(dist2).  Unsigned mode: sdf = sqrt(dist2).
-#include "ngp_device.h"
+#include "mesh_bvh.h"
 
 namespace ngp {
 
-constexpr int MESH_SDF_MAX_DEPTH = 24;
-constexpr int MESH_SDF_MAX_LEAF = NGP_MESH_SDF_MAX_LEAF;
 constexpr int MESH_SDF_QUERY_BLOCK = 64;                        // one wave per block: a walk is as long as its slowest lane, and a small batch
                                                                // (16 384 points = 256 waves) then reaches every CU
 constexpr float MESH_SDF_WIDEN = 1.0f / 262144.0f;             // 2^-18: of the leaf box's longest side
 constexpr float MESH_SDF_DEFLATE = 1.0f - 1.0f / 262144.0f;    // 1 - 2^-18: on the squared lower bound
-
-struct MeshTree {
-    long long leaves;        // ceil(n_faces / leaf_size)
-    long long padded;        // P
-    int depth;               // log2 P
-};
-__host__ __forceinline__ bool mesh_tree(long long n_faces, int leaf_size, MeshTree& t) {
-    if (n_faces < 1 || n_faces > 0x7fffffffll || leaf_size < 1 || leaf_size > MESH_SDF_MAX_LEAF) return false;
-    t.leaves = (n_faces + leaf_size - 1) / leaf_size;
-    t.padded = 1;
-    t.depth = 0;
-    while (t.padded < t.leaves) { t.padded <<= 1; ++t.depth; }
-    return t.depth <= MESH_SDF_MAX_DEPTH;
-}
-
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3_load(const float* __restrict__ p, long long i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
-__device__ __forceinline__ V3 v3_sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float v3_dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 
 __global__ void __launch_bounds__(256) mesh_sdf_leaf_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
                                                             const int32_t* __restrict__ order, int n_faces, int leaf_size, int padded,

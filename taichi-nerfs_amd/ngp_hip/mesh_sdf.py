@@ -4,6 +4,9 @@
     d = target(points)                                                 # MeshDistance(sdf, closest, face, feature), one launch
     x = target.sample(2**16, sigma=0.01, uniform_fraction=0.25, generator=g)     # training points: near the surface + in the box
     surface_distance(mesh_a, mesh_b, 2**16)                            # how far two surfaces are apart, both ways
+    hit = target.raycast(rays_o, rays_d)                               # MeshRayHit(t, face, bary, side): the first face along each ray
+    target.visible(a, b)                                               # bool [n]: nothing of the mesh between a and b
+    render_mesh(target, K, c2w, (W, H))                                # depth, normal, mask and face images from a camera
 
 The sign follows the angle-weighted pseudonormal of the nearest feature (Baerentzen & Aanaes 2005), which is exact for a closed,
 consistently oriented 2-manifold whatever the dihedral angles.  On an open mesh it is the side of the nearest feature; a self-intersecting
@@ -39,6 +42,54 @@ class MeshDistance(_MeshDistance):
         length = torch.linalg.norm(r, dim=1, keepdim=True)
         sign = torch.where(self.sdf < 0, -1.0, 1.0).to(r.dtype)[:, None]
         return torch.where(length > 0, sign * r / length.clamp_min(torch.finfo(r.dtype).tiny), torch.zeros_like(r))
+
+
+class _MeshRayHit(NamedTuple):
+    t: torch.Tensor              # [n] f32: the ray parameter of the hit in units of |d|; +inf on a miss
+    face: torch.Tensor           # [n] int32: the face hit, a row of the faces MeshSDF was given; -1 on a miss
+    bary: torch.Tensor           # [n,2] f32: (v, w), the hit point is a + v (b - a) + w (c - a); 0 on a miss
+    side: torch.Tensor           # [n] int32: +1 the front of the face (d . cross(b - a, c - a) < 0), -1 its back, 0 a miss
+
+
+class MeshRayHit(_MeshRayHit):
+    """What MeshSDF.raycast returns; unpacks as (t, face, bary, side).  All detached: the query has no gradients."""
+
+    def __new__(cls, t, face, bary, side, mesh=None):
+        self = super().__new__(cls, t, face, bary, side)
+        self.mesh = mesh
+        return self
+
+    @property
+    def hit(self):
+        """bool [n]: the ray met the mesh."""
+        return torch.isfinite(self.t)
+
+    def points(self, rays_o, rays_d):
+        """[n,3]: o + t d; the origin on a miss."""
+        return rays_o + torch.where(self.hit, self.t, torch.zeros_like(self.t))[:, None] * rays_d
+
+    def normals(self, smooth=None):
+        """[n,3] unit normals at the hit points, turned towards the ray's origin; 0 on a miss.  The geometric normal of the face, or,
+        with smooth = per-vertex normals [V,3] (a Mesh's), those of the face's corners interpolated by `bary`.  Needs details=True."""
+        if self.face is None:
+            raise ValueError("normals() needs the face, bary and side of a raycast with details=True")
+        hit = self.face >= 0
+        corners = self.mesh.faces[self.face.clamp_min(0).long()].long()                  # [n,3] vertex indices
+        a, b, c = (self.mesh.vertices[corners[:, k]] for k in range(3))
+        geometric = torch.cross(b - a, c - a, dim=1)
+        front = (self.side > 0)[:, None]
+        if smooth is None:
+            n = torch.where(front, geometric, -geometric)
+        else:
+            sn = torch.as_tensor(smooth, dtype=torch.float32, device=a.device)
+            if tuple(sn.shape) != tuple(self.mesh.vertices.shape):
+                raise ValueError("smooth must hold one normal per vertex, %s, got %s" % (tuple(self.mesh.vertices.shape), tuple(sn.shape)))
+            v, w = self.bary[:, :1], self.bary[:, 1:]
+            n = sn[corners[:, 0]] * (1.0 - v - w) + sn[corners[:, 1]] * v + sn[corners[:, 2]] * w
+            agrees = ((n * geometric).sum(1, keepdim=True) >= 0) == front                  # the interpolated normal, on the side that was hit
+            n = torch.where(agrees, n, -n)
+        length = torch.linalg.norm(n, dim=1, keepdim=True)
+        return torch.where(hit[:, None] & (length > 0), n / length.clamp_min(torch.finfo(n.dtype).tiny), torch.zeros_like(n))
 
 
 # ---- per-mesh data, on the host in float64 -----------------------------------------------------------------------------------------------
@@ -188,6 +239,22 @@ class MeshSDF:
                                  self.vertex_normals, details=details)
         return MeshDistance(*out, points=x)
 
+    def raycast(self, rays_o, rays_d, t_min=0.0, t_max=float("inf"), any_hit=False, cull=None, details=True):
+        """rays_o, rays_d [n,3] f32 on the device (directions need not be normalised) -> MeshRayHit(t [n], face [n], bary [n,2], side [n]):
+        the first face along o + t d with t in [t_min, t_max] (csrc/mesh_raycast.hip: the watertight test, no ray slips between two faces
+        that share an edge or a vertex); details=False fills only t.  any_hit: stop at the first face met, the occlusion query -- t and
+        face are then those of SOME face in range.  cull: None, "back" or "front" (a face shows its front where d . cross(b - a, c - a)
+        < 0).  There are no gradients: the outputs are detached.  Works with signed=False: the pseudonormals are not used."""
+        out = ops.mesh_raycast(rays_o.detach(), rays_d.detach(), self.vertices, self.faces, self.order, self.boxes, self.leaf_size,
+                               t_min=t_min, t_max=t_max, any_hit=any_hit, cull=cull, details=details)
+        return MeshRayHit(*out, mesh=self)
+
+    def visible(self, a, b, eps=1e-4):
+        """bool [n]: the open segment from a [n,3] to b [n,3] meets no face -- any-hit along d = b - a with t in [eps, 1 - eps]."""
+        a = a.detach()
+        d = (b.detach() - a).contiguous()
+        return ~self.raycast(a, d, t_min=float(eps), t_max=1.0 - float(eps), any_hit=True, details=False).hit
+
     def sample(self, n, sigma=0.01, uniform_fraction=0.25, generator=None, pad=0.1):
         """Training points [n,3] f32: round(n (1 - uniform_fraction)) on the surface (area-weighted faces, uniform barycentrics) moved by a
         normal-distributed offset of scale sigma per axis, then the rest uniform in the bounding box padded by `pad` x its longest side
@@ -220,4 +287,32 @@ def surface_distance(mesh_a, mesh_b, n=65536, generator=None, leaf_size=4):
     return out
 
 
-__all__ = ["Mesh", "MeshDistance", "MeshSDF", "morton_order", "pseudonormals", "sample_surface", "surface_distance", "weld_vertices"]
+def render_mesh(target, K, c2w, img_wh, cull=None, smooth=None):
+    """Depth, normal, mask and face images of a mesh seen from one camera: target a MeshSDF or a Mesh (a hierarchy is then built here,
+    unsigned), K [3,3] intrinsics, c2w [3,4] (right, down, front | position), img_wh = (W, H) -> dict(depth [H,W] f32, normal [H,W,3]
+    f32, mask [H,W] bool, face [H,W] int32).  The rays are those of get_ray_directions / get_rays, their directions normalised as
+    render_surface_traced normalises them: depth is the EUCLIDEAN DISTANCE from the camera centre along the pixel's ray -- what
+    render_surface_traced reports as `depth` and trace_surface as `t`, and what render() reports for unit directions -- so the images
+    subtract directly where both hit.  Where the ray misses, depth is +inf (the traced renderers write 0 there): mask = isfinite(depth).
+    normal: unit, towards the camera, the face's own or, with smooth = True (a Mesh's vertex normals) or a [V,3] tensor, interpolated;
+    0 on a miss.  cull as MeshSDF.raycast."""
+    from .rays import get_ray_directions, get_rays
+    mesh_normals = getattr(target, "normals", None)
+    if not isinstance(target, MeshSDF):
+        target = MeshSDF(target.vertices, target.faces, signed=False)
+    if smooth is True:
+        if mesh_normals is None or callable(mesh_normals):
+            raise ValueError("smooth=True needs a Mesh with vertex normals; pass the normals [V,3] instead")
+        smooth = mesh_normals
+    w, h = int(img_wh[0]), int(img_wh[1])
+    dev = target.vertices.device
+    K = torch.as_tensor(K, dtype=torch.float32)
+    directions = get_ray_directions(h, w, K, device=dev)
+    rays_o, rays_d = get_rays(directions, torch.as_tensor(c2w, dtype=torch.float32).to(dev))
+    rays_d = (rays_d / torch.linalg.norm(rays_d, dim=1, keepdim=True)).contiguous()
+    hit = target.raycast(rays_o.contiguous(), rays_d, cull=cull)
+    return {"depth": hit.t.view(h, w), "normal": hit.normals(smooth).view(h, w, 3), "mask": hit.hit.view(h, w), "face": hit.face.view(h, w)}
+
+
+__all__ = ["Mesh", "MeshDistance", "MeshRayHit", "MeshSDF", "morton_order", "pseudonormals", "render_mesh", "sample_surface", "surface_distance",
+           "weld_vertices"]

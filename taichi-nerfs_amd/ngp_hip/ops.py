@@ -921,6 +921,36 @@ def mesh_sdf_query(points, vertices, faces, order, boxes, leaf_size=4, edge_norm
     return sdf, closest, face, feature
 
 
+RAYCAST_ANY_HIT, RAYCAST_CULL_BACK, RAYCAST_CULL_FRONT = (_lib_mod._ABI.defines[k] for k in
+                                                          ("NGP_RAYCAST_ANY_HIT", "NGP_RAYCAST_CULL_BACK", "NGP_RAYCAST_CULL_FRONT"))
+
+
+def mesh_raycast(rays_o, rays_d, vertices, faces, order, boxes, leaf_size=4, t_min=0.0, t_max=float("inf"), any_hit=False, cull=None,
+                 details=True):
+    """First face along every ray o + t d (csrc/mesh_raycast.hip), rays_o / rays_d [n,3] f32, in the tree of mesh_bvh_build -> (t [n]: +inf
+    on a miss, face [n] int32: -1, bary [n,2]: 0, side [n] int32: +1 front, -1 back, 0 miss); details=False: only t, the others None (the
+    same bits).  t in [t_min, t_max], in units of |d|.  any_hit: stop at the first accepted face (occlusion).  cull: None, "back" or
+    "front"."""
+    n_faces, need = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or tuple(rays_d.shape) != tuple(rays_o.shape):
+        raise ValueError("rays_o and rays_d must both be [n,3], got %s and %s" % (tuple(rays_o.shape), tuple(rays_d.shape)))
+    if cull not in (None, "back", "front"):
+        raise ValueError("cull must be None, 'back' or 'front', got %r" % (cull,))
+    _dev(rays_o, torch.float32, "rays_o"); _dev(rays_d, torch.float32, "rays_d"); _dev(boxes, torch.float32, "boxes")
+    if boxes.numel() * 4 != need:
+        raise ValueError("boxes holds %d bytes, the tree of %d faces in leaves of %d needs %d" % (boxes.numel() * 4, n_faces, leaf_size, need))
+    flags = (RAYCAST_ANY_HIT if any_hit else 0) | {None: 0, "back": RAYCAST_CULL_BACK, "front": RAYCAST_CULL_FRONT}[cull]
+    n, dev = rays_o.shape[0], rays_o.device
+    t = torch.empty(n, device=dev, dtype=torch.float32)
+    face = torch.empty(n, device=dev, dtype=torch.int32) if details else None
+    bary = torch.empty(n, 2, device=dev, dtype=torch.float32) if details else None
+    side = torch.empty(n, device=dev, dtype=torch.int32) if details else None
+    check(_lib().ngp_mesh_raycast(_ptr(rays_o), _ptr(rays_d), n, _ptr(vertices), _ptr(faces), _ptr(order), _ptr(boxes), n_faces,
+                                  int(leaf_size), float(t_min), float(t_max), flags, _ptr(t), _ptr(face), _ptr(bary), _ptr(side), _stream()),
+          "ngp_mesh_raycast")
+    return t, face, bary, side
+
+
 # ---------------------------------------------------------------------------------------------------- surface rendering
 def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
     _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
