@@ -3,6 +3,7 @@ that is measured at both ends.  Needs no data file.
 
     python examples/fit_sdf_mesh.py
     python examples/fit_sdf_mesh.py --steps 200 --n 4096 --log2_T 14 --levels 8 --max_res 128 --target_resolution 32 --resolution 48
+    python examples/fit_sdf_mesh.py --target two_spheres --sign winding
 
 The target is made here: a torus (R 0.25, r 0.1, centred in [-0.5, 0.5]^3), extracted with marching tetrahedra from its analytic SDF at
 --target_resolution cells per axis.  MeshSDF answers the distance to THAT MESH (BVH closest-point query, csrc/mesh_sdf.hip) at the
@@ -11,7 +12,14 @@ twice differentiable, + MLP, starting as a sphere of radius 0.25) is fitted with
     loss = mean |f - sdf_mesh| + eikonal_weight * mean (|grad_x f| - 1)^2
 as in fit_sdf_eikonal.py, and its zero set is extracted again at --resolution.  One JSON line reports the SDF loss first / last, the
 eikonal error, surface_distance between the target and the result (and the untrained sphere) in units of the extraction cell, topology()
-of both meshes and the time of the distance query per step."""
+of both meshes and the time of the distance query per step.
+
+--target two_spheres replaces the torus by two overlapping icospheres (radius 0.2, centres 0.25 apart, concatenated as they are: two
+closed shells, one inside the other in part).  With --sign pseudonormal (the default) the distance is negative only where the NEAREST
+face says so, so the part of each sphere inside the other keeps a spurious wall and the field is fitted to it; --sign winding takes
+the sign from the generalized winding number (csrc/mesh_winding.hip) and the target is the union.  `sign_disagreement` in the report is
+the share of one batch of training points on which the two signs differ, and `sign_wrong` the share on which the chosen sign differs
+from the analytic union of the two spheres (two_spheres only; points nearer to either sphere than 0.02 are left out)."""
 import argparse
 import json
 import os
@@ -29,6 +37,48 @@ BOUNDS = ((-0.5, -0.5, -0.5), (0.5, 0.5, 0.5))
 
 def torus_sdf(x, R=0.25, r=0.1):
     return torch.sqrt((torch.linalg.norm(x[:, :2], dim=1) - R) ** 2 + x[:, 2] ** 2) - r
+
+
+TWO_SPHERES = (((-0.125, 0.0, 0.0), (0.125, 0.0, 0.0)), 0.2)
+
+
+def icosphere(subdivisions, centre, radius):
+    """(vertices [V,3] f32, faces [T,3] int32) of a subdivided icosahedron, counter-clockwise seen from outside."""
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+         (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    v = [torch.tensor(x, dtype=torch.float64) / (1.0 + t * t) ** 0.5 for x in v]
+    for _ in range(subdivisions):
+        mid, out = {}, []
+
+        def m(i, j):
+            key = (min(i, j), max(i, j))
+            if key not in mid:
+                x = v[i] + v[j]
+                v.append(x / torch.linalg.norm(x))
+                mid[key] = len(v) - 1
+            return mid[key]
+        for a, b, c in f:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            out += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = out
+    return (torch.tensor(centre, dtype=torch.float64) + radius * torch.stack(v)).float(), torch.tensor(f, dtype=torch.int32)
+
+
+def two_spheres(subdivisions, device):
+    """The built-in target on which the two signs differ: two overlapping closed shells in one face list, unwelded."""
+    from ngp_hip.mesh import Mesh
+    centres, radius = TWO_SPHERES
+    parts = [icosphere(subdivisions, c, radius) for c in centres]
+    vertices = torch.cat([p[0] for p in parts])
+    faces = torch.cat([parts[0][1], parts[1][1] + parts[0][0].shape[0]])
+    return Mesh(vertices.to(device), faces.to(device), None)
+
+
+def two_spheres_sdf(x):
+    centres, radius = TWO_SPHERES
+    return torch.stack([torch.linalg.norm(x - torch.tensor(c, device=x.device), dim=1) for c in centres]).min(0).values - radius
 
 
 def fit(field, target_sdf, steps, n, sigma, uniform_fraction, lr, eikonal_weight, gen):
@@ -74,6 +124,9 @@ def main(argv=None):
     ap.add_argument("--resolution", type=int, default=128, help="cells per axis of the result's extraction")
     ap.add_argument("--compare_n", type=int, default=65536, help="samples per direction of surface_distance")
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--target", choices=("torus", "two_spheres"), default="torus")
+    ap.add_argument("--sign", choices=("pseudonormal", "winding"), default="pseudonormal", help="where the sign of the distance comes from")
+    ap.add_argument("--subdivisions", type=int, default=4, help="two_spheres: subdivisions of each icosphere (4: 5120 faces each)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("this example needs the GPU: libngp_hip has no CPU path")
@@ -82,8 +135,19 @@ def main(argv=None):
     from ngp_hip import MeshSDF, SDFField, surface_distance
     from ngp_hip.mesh import extract_mesh, topology
 
-    target = extract_mesh(torus_sdf, args.target_resolution, 0.0, bounds=BOUNDS, sign=-1, normals=None, device=dev)
-    target_sdf = MeshSDF.from_mesh(target)
+    if args.target == "torus":
+        target = extract_mesh(torus_sdf, args.target_resolution, 0.0, bounds=BOUNDS, sign=-1, normals=None, device=dev)
+    else:
+        target = two_spheres(args.subdivisions, dev)
+    target_sdf = MeshSDF.from_mesh(target, sign=args.sign)
+    other = MeshSDF.from_mesh(target, sign="winding" if args.sign == "pseudonormal" else "pseudonormal")
+    probe = target_sdf.sample(args.n, args.sigma, args.uniform_fraction, torch.Generator().manual_seed(args.seed + 1)).clamp_(-0.5, 0.5)
+    chosen = target_sdf(probe, details=False).sdf
+    signs = {"sign_disagreement": float(((chosen < 0) != (other(probe, details=False).sdf < 0)).float().mean())}
+    if args.target == "two_spheres":
+        truth = two_spheres_sdf(probe)
+        clear = torch.stack([(torch.linalg.norm(probe - torch.tensor(c, device=dev), dim=1) - TWO_SPHERES[1]).abs() for c in TWO_SPHERES[0]]).min(0).values > 0.02
+        signs["sign_wrong"] = float(((chosen < 0) != (truth < 0))[clear].float().mean())
     field = SDFField(scale=0.5, levels=args.levels, log2_T=args.log2_T, max_res=args.max_res).to(dev)
     cell = 1.0 / args.resolution
 
@@ -102,6 +166,7 @@ def main(argv=None):
     result = extract()
     info = {"steps": args.steps, "points_per_step": args.n, "levels": args.levels, "log2_T": args.log2_T, "max_res": args.max_res,
             "target_resolution": args.target_resolution, "resolution": args.resolution, "target_faces": int(target.faces.shape[0]),
+            "target_name": args.target, "sign": args.sign, **signs,
             "sdf_loss_first": hist[0][0], "sdf_loss_last": hist[-1][0], "eikonal_error_first": hist[0][1], "eikonal_error_last": hist[-1][1],
             "surface_distance_untrained": untrained, "surface_distance": compare(result),
             "topology_target": topology(target), "topology_result": topology(result),

@@ -763,6 +763,31 @@ int ngp_mesh_raycast(const float* rays_o, const float* rays_d, int n,
                      float* t /*[n]*/, int32_t* face /*[n], may be NULL*/, float* bary /*[n,2], may be NULL*/,
                      int32_t* side /*[n], may be NULL*/, void* stream);
 
+/* ---- winding number of a triangle mesh: inside / outside for open, overlapping and unwelded meshes (csrc/mesh_winding.hip; DESIGN.md
+ * section 3).  vertices, faces, order, boxes, n_faces, leaf_size: the tree ngp_mesh_bvh_build made, read only.
+ * w(q) = (1 / 4 pi) sum_f Omega_f(q), Omega_f = 2 atan2(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) with a, b, c the corners
+ * minus q, in f32 (the formula in csrc/mesh_winding.hip), and 0 where a . (b x c) == 0.  With cross(b - a, c - a) pointing outward a
+ * closed mesh gives +1 inside and 0 outside; a point on a vertex and a face without area add 0.
+ * moments: f32 [2 P - 1, 20], 16-byte aligned, one row per node of the tree:
+ *     0..2 p (the area-weighted centroid of the faces below; the box centre where their area sums to 0)
+ *     3 r (the distance from p to the farthest corner of the node's box, rounded upwards; -1: an empty node)
+ *     4..6 N = sum 0.5 cross(b - a, c - a)    7 A = sum of the areas    8..16 T = sum (centroid_f - p) (x) (area vector)_f, row major
+ *     17 1 for a node with faces, 0 for an empty one    18, 19 0
+ * winding_bytes : the size of `moments`; -1 wherever ngp_mesh_bvh_bytes refuses
+ * winding_build : fills moments from the tree, one launch per level, no atomics: the same mesh and order give the same bytes
+ * winding_query : one launch, one lane per point, a preorder walk.  A node with d = p - q is accepted iff d.d > (beta r)^2 and then adds
+ *                 N.d / |d|^3 (order_terms >= 1) + trace(T) / |d|^3 - 3 d.T d / |d|^5 (order_terms 2) in place of its faces; a leaf that
+ *                 is not accepted adds Omega of each of its faces.  beta = +inf accepts nothing: the exact sum.  The sum is f32 in walk
+ *                 order: winding [n] depends on its point and the tree alone.  A point with a coordinate that is not finite gets NaN.
+ * All return -1 without a launch for a null required pointer, a size bvh_bytes refuses or n < 0; winding_query also for a beta below 1
+ * or NaN and an order_terms other than 1 or 2, and it returns 0 without a launch for n = 0 (points and winding may then be null). */
+long long ngp_mesh_winding_bytes(long long n_faces, int leaf_size);
+int ngp_mesh_winding_build(const float* vertices, const int32_t* faces, const int32_t* order, const float* boxes, int n_faces,
+                           int leaf_size, float* moments, void* stream);
+int ngp_mesh_winding_query(const float* points, int n, const float* vertices, const int32_t* faces, const int32_t* order,
+                           const float* moments, int n_faces, int leaf_size, float beta, int order_terms /* 1 or 2 */,
+                           float* winding /*[n]*/, void* stream);
+
 /* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
  * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
  * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],

@@ -1,6 +1,6 @@
-// mesh_bvh.h -- what the two queries against the box hierarchy of a triangle mesh share: the shape of the implicit tree (mesh_sdf.hip
+// mesh_bvh.h -- what the three queries against the box hierarchy of a triangle mesh share: the shape of the implicit tree (mesh_sdf.hip
 // builds it and states its layout), the limits the entries refuse beyond, and the three-float helpers.  mesh_sdf.hip asks the tree for
-// the nearest face of a point, mesh_raycast.hip for the first face along a ray.
+// the nearest face of a point, mesh_raycast.hip for the first face along a ray, mesh_winding.hip for the winding number of a point.
 #pragma once
 #include "ngp_device.h"
 

@@ -6,11 +6,17 @@
     surface_distance(mesh_a, mesh_b, 2**16)                            # how far two surfaces are apart, both ways
     hit = target.raycast(rays_o, rays_d)                               # MeshRayHit(t, face, bary, side): the first face along each ray
     target.visible(a, b)                                               # bool [n]: nothing of the mesh between a and b
+    w = target.winding(points)                                         # [n]: the generalized winding number, 1 inside, 0 outside
+    target.inside(points)                                              # bool [n]: w >= 0.5
+    MeshSDF.from_mesh(scan, sign="winding")                            # the sign of the distance from the winding number
     render_mesh(target, K, c2w, (W, H))                                # depth, normal, mask and face images from a camera
 
 The sign follows the angle-weighted pseudonormal of the nearest feature (Baerentzen & Aanaes 2005), which is exact for a closed,
-consistently oriented 2-manifold whatever the dihedral angles.  On an open mesh it is the side of the nearest feature; a self-intersecting
-mesh gets no promise.  The contract is DESIGN.md section 3, "Distance to a triangle mesh"."""
+consistently oriented 2-manifold whatever the dihedral angles.  On an open mesh it is the side of the nearest feature, and on a
+self-intersecting mesh, overlapping closed shells or an unwelded soup it is wrong without a warning wherever the nearest face belongs to
+a part that lies inside another.  For those, sign="winding" takes the sign from the generalized winding number of the whole mesh
+(csrc/mesh_winding.hip: negative where w >= 0.5), which degrades gracefully with holes and counts overlapping shells as their union.
+The contract is DESIGN.md section 3, "Distance to a triangle mesh" and "Winding number of a triangle mesh"."""
 from typing import NamedTuple
 
 import numpy as np
@@ -181,9 +187,13 @@ class MeshSDF:
     triangle soup otherwise has one-face edges everywhere and the edge and vertex normals are those of single faces.  leaf_size: faces
     per leaf of the hierarchy, 1..8.  Raises ValueError for a wrong shape or dtype, an index outside [0, V) or a mesh without a face
     that has three different indices, all before any launch.  Faces with two equal indices are dropped (`n_dropped`); the `face` a query
-    returns still counts rows of the `faces` given here."""
+    returns still counts rows of the `faces` given here.  sign (with signed=True): "pseudonormal", or "winding" -- negative where the
+    generalized winding number is at least 0.5 (beta 2, order 2), right for open, overlapping and unwelded meshes; no pseudonormals are
+    then computed."""
 
-    def __init__(self, vertices, faces, signed=True, weld=False, leaf_size=4, device="cuda"):
+    def __init__(self, vertices, faces, signed=True, weld=False, leaf_size=4, device="cuda", sign="pseudonormal"):
+        if sign not in ("pseudonormal", "winding"):
+            raise ValueError("sign must be 'pseudonormal' or 'winding', got %r" % (sign,))
         v, f = _as_numpy(vertices), _as_numpy(faces)
         if v.ndim != 2 or v.shape[1] != 3 or v.dtype != np.float32:
             raise ValueError("vertices must be float32 [V,3], got %s %s" % (v.dtype, v.shape))
@@ -206,11 +216,12 @@ class MeshSDF:
         if not keep.any():
             raise ValueError("every face of the mesh uses a vertex twice: nothing to measure a distance to")
         kept = np.nonzero(keep)[0]
-        self.signed, self.leaf_size = bool(signed), int(leaf_size)
+        self.signed, self.leaf_size, self.sign = bool(signed), int(leaf_size), sign
+        self._moments = None
         self.vertices = torch.from_numpy(np.ascontiguousarray(v)).to(device)
         self.faces = torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(device)
         self.edge_normals = self.vertex_normals = None
-        if signed:
+        if signed and sign == "pseudonormal":
             en = np.zeros((len(f), 3, 3))
             en[kept], vn = pseudonormals(v, f[kept])
             self.edge_normals = torch.from_numpy(en.astype(np.float32)).to(device)
@@ -237,7 +248,35 @@ class MeshSDF:
         x = points.detach()
         out = ops.mesh_sdf_query(x, self.vertices, self.faces, self.order, self.boxes, self.leaf_size, self.edge_normals,
                                  self.vertex_normals, details=details)
+        if self.signed and self.sign == "winding":
+            out = (torch.where(self.winding(x) >= 0.5, -out[0], out[0]),) + tuple(out[1:])
         return MeshDistance(*out, points=x)
+
+    @property
+    def moments(self):
+        """f32 [2 P - 1, 20]: the per-node moments of the winding number (csrc/mesh_winding.hip), built on first use."""
+        if self._moments is None:
+            self._moments = ops.mesh_winding_build(self.vertices, self.faces, self.order, self.boxes, self.leaf_size)
+        return self._moments
+
+    def winding(self, points, beta=2.0, order=2):
+        """points [n,3] f32 on the device -> the generalized winding number [n] f32 (csrc/mesh_winding.hip): 1 inside a closed mesh whose
+        faces are counter-clockwise seen from outside, 0 outside, fractional near a hole, the number of enclosing shells where closed
+        parts overlap.  A node of the hierarchy farther than beta x its radius is replaced by its expansion of `order` terms (1 or 2);
+        beta = inf sums every face.  Detached: there are no gradients.  Works with signed=False."""
+        x = points.detach()                         # checked here as ops would: before the first use builds the moments
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise ValueError("points must be [n,3], got %s" % (tuple(x.shape),))
+        if not float(beta) >= 1.0:
+            raise ValueError("beta must be at least 1, got %r" % (beta,))
+        if order not in (1, 2):
+            raise ValueError("order must be 1 or 2, got %r" % (order,))
+        ops._dev(x, torch.float32, "points")
+        return ops.mesh_winding_query(x, self.vertices, self.faces, self.order, self.moments, self.leaf_size, beta=beta, order_terms=order)
+
+    def inside(self, points, **kw):
+        """bool [n]: winding(points, **kw) >= 0.5."""
+        return self.winding(points, **kw) >= 0.5
 
     def raycast(self, rays_o, rays_d, t_min=0.0, t_max=float("inf"), any_hit=False, cull=None, details=True):
         """rays_o, rays_d [n,3] f32 on the device (directions need not be normalised) -> MeshRayHit(t [n], face [n], bary [n,2], side [n]):

@@ -951,6 +951,54 @@ def mesh_raycast(rays_o, rays_d, vertices, faces, order, boxes, leaf_size=4, t_m
     return t, face, bary, side
 
 
+MESH_WINDING_ROW = 20        # floats per node of `moments` (include/ngp_hip.h publishes the columns)
+
+
+def _mesh_winding_bytes(n_faces, leaf_size):
+    need = _lib().ngp_mesh_winding_bytes(n_faces, int(leaf_size))
+    if need < 0:
+        raise ValueError("%d faces in leaves of %d make a tree the winding number refuses" % (n_faces, leaf_size))
+    return need
+
+
+def mesh_winding_build(vertices, faces, order, boxes, leaf_size=4):
+    """The per-node moments of csrc/mesh_winding.hip (centroid, radius, area vector, area, second-order tensor) over the tree of
+    mesh_bvh_build -> moments f32 [2 P - 1, 20]."""
+    n_faces, need = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
+    _dev(boxes, torch.float32, "boxes")
+    if boxes.numel() * 4 != need:
+        raise ValueError("boxes holds %d bytes, the tree of %d faces in leaves of %d needs %d" % (boxes.numel() * 4, n_faces, leaf_size, need))
+    moments = torch.empty(_mesh_winding_bytes(n_faces, leaf_size) // (4 * MESH_WINDING_ROW), MESH_WINDING_ROW, device=vertices.device,
+                          dtype=torch.float32)
+    check(_lib().ngp_mesh_winding_build(_ptr(vertices), _ptr(faces), _ptr(order), _ptr(boxes), n_faces, int(leaf_size), _ptr(moments),
+                                        _stream()), "ngp_mesh_winding_build")
+    return moments
+
+
+def mesh_winding_query(points, vertices, faces, order, moments, leaf_size=4, beta=2.0, order_terms=2):
+    """Generalized winding number of every point [n,3] f32 against the mesh (csrc/mesh_winding.hip) -> w [n] f32: 1 inside a closed,
+    outward-oriented mesh, 0 outside, in between near holes.  A node of the tree farther than beta x its radius is replaced by its
+    expansion of order_terms (1 or 2); beta >= 1, beta = inf: the exact sum over all faces."""
+    n_faces, _ = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("points must be [n,3], got %s" % (tuple(points.shape),))
+    if not float(beta) >= 1.0:
+        raise ValueError("beta must be at least 1 (a node is accepted only from outside its radius), got %r" % (beta,))
+    if order_terms not in (1, 2):
+        raise ValueError("order_terms must be 1 or 2, got %r" % (order_terms,))
+    _dev(points, torch.float32, "points"); _dev(moments, torch.float32, "moments")
+    need = _mesh_winding_bytes(n_faces, leaf_size)
+    if moments.numel() * 4 != need:
+        raise ValueError("moments holds %d bytes, the tree of %d faces in leaves of %d needs %d" % (moments.numel() * 4, n_faces, leaf_size, need))
+    if moments.data_ptr() % 16:
+        raise ValueError("moments must start at a multiple of 16 bytes: the query reads its rows as 16-byte vectors")
+    n = points.shape[0]
+    winding = torch.empty(n, device=points.device, dtype=torch.float32)
+    check(_lib().ngp_mesh_winding_query(_ptr(points), n, _ptr(vertices), _ptr(faces), _ptr(order), _ptr(moments), n_faces, int(leaf_size),
+                                        float(beta), int(order_terms), _ptr(winding), _stream()), "ngp_mesh_winding_query")
+    return winding
+
+
 # ---------------------------------------------------------------------------------------------------- surface rendering
 def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
     _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
