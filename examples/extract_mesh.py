@@ -8,7 +8,9 @@
 examples/fit_sdf_eikonal.py does, and extracts the zero level with sign=-1 (solid where f < 0).  The other two modes extract the surface
 density = threshold of an Instant-NGP model; the default threshold is the occupancy threshold of the training loop,
 0.01 * MAX_SAMPLES / sqrt(3).  The file type follows the suffix of --out (.ply binary little-endian, .obj text).  One JSON line reports
-V, T, the Euler characteristic V - E + T, the number of boundary edges (0 = closed surface) and the times."""
+V, T, the Euler characteristic V - E + T, the number of boundary edges (0 = closed surface) and the times.
+--keep_largest K and --min_component_faces N (both off by default) remove floaters before the file is written (ngp_hip.clean_mesh:
+connected components on the device) and print its report and the topology before and after."""
 import argparse
 import json
 import math
@@ -101,6 +103,9 @@ def main(argv=None):
     ap.add_argument("--out", default="mesh.ply", help=".ply or .obj")
     ap.add_argument("--compare", default=None, metavar="PATH.ply",
                     help="also report surface_distance (mean / max, both ways) between the extracted mesh and this one (.ply or .obj)")
+    ap.add_argument("--keep_largest", type=int, default=None, metavar="K",
+                    help="clean the mesh before writing it: keep the K connected components of the largest area (ngp_hip.clean_mesh)")
+    ap.add_argument("--min_component_faces", type=int, default=0, metavar="N", help="clean the mesh: drop components of fewer than N faces")
     ap.add_argument("--scale", type=float, default=0.5)
     # the --sdf fit (fit_sdf_eikonal.py's options); --max_res also sizes the NGP of --ckpt
     ap.add_argument("--steps", type=int, default=500)
@@ -154,11 +159,20 @@ def main(argv=None):
         info.update(threshold=thr)
     torch.cuda.synchronize()
     t2 = time.time()
+    if args.keep_largest is not None or args.min_component_faces > 0:        # off by default: the output is then what it always was
+        before = mesh.topology(msh)
+        msh, report = mesh.clean_mesh(msh, keep_largest=args.keep_largest, min_faces=args.min_component_faces)
+        torch.cuda.synchronize()
+        report.pop("kept")
+        info.update(clean=dict(report, before=before, seconds=time.time() - t2))
+        print("clean_mesh:", json.dumps(info["clean"]))
+        print("topology before:", json.dumps(before), "after:", json.dumps(mesh.topology(msh)))
+    t_write = time.time()
     (mesh.write_ply if args.out.endswith(".ply") else mesh.write_obj)(args.out, msh)
     t3 = time.time()
     info.update(mesh.topology(msh))
     info.update(resolution=args.resolution, normals=args.normals, out=args.out, prepare_seconds=t1 - t0, extract_seconds=t2 - t1,
-                write_seconds=t3 - t2)
+                write_seconds=t3 - t_write)
     if args.compare:
         from ngp_hip import surface_distance
         other = (mesh.read_ply if args.compare.endswith(".ply") else mesh.read_obj)(args.compare)

@@ -788,6 +788,51 @@ int ngp_mesh_winding_query(const float* points, int n, const float* vertices, co
                            const float* moments, int n_faces, int leaf_size, float beta, int order_terms /* 1 or 2 */,
                            float* winding /*[n]*/, void* stream);
 
+/* ---- connected components of a triangle mesh: labels, a per-component table, sub-mesh selection (csrc/mesh_components.hip; DESIGN.md
+ * section 3).  faces int32 [T,3], n_vertices V, 1 <= T, V <= 2^31 - 1 (the package answers T = 0 and V = 0 without a call).  Two
+ * vertices are connected when some face names both.  A face with an index outside [0, V) is bad: it joins nothing and gets face
+ * component -1; a face that repeats an index still joins its vertices.  A vertex named by no good face is unused: component -1.
+ * Components are numbered 0 .. C - 1 by increasing smallest vertex index.
+ * components_bytes : the size of `workspace` for label and select_count (about max(T, V) + 4 V bytes)
+ * components_rounds: n_rounds rounds of the min-index union-find on parent int32 [V] (parent[x] <= x; the caller starts it at
+ *                    parent[x] = x): a hook pass over the faces, then a compress pass over the vertices.  changed int32 [n_rounds],
+ *                    zeroed by the caller: changed[r] = 1 iff hook pass r moved something; passes behind the first that did not
+ *                    return at once.  The labelling is complete after a pass with changed[r] = 0; at most V passes are needed.
+ * components_label : after such a pass: vertex_component int32 [V], face_component int32 [T], counts int32 [3] = {C, bad faces,
+ *                    unused vertices}, on the device
+ * components_edge_keys : keys int64 [3 T]: min V + max per edge of every good face with three distinct indices, INT64_MAX otherwise
+ * components_table : sorted_keys = those keys in ascending order.  table int32 [C,6] = vertices, faces, edges (distinct keys),
+ *                    boundary edges (keys used once), non-manifold edges (keys used three or more times), euler = vertices - edges
+ *                    + faces.  An edge belongs to the component of its ends.  Integer atomics only.
+ * components_measure : order int64 [T] = the faces sorted by (face component, index), bad faces first; face_start int32 [C + 1]: where
+ *                    component c starts in `order`; block_start int32 [C + 1]: the exclusive prefix sums of ceil(faces_c / 64);
+ *                    partials: partial_bytes(T, C) bytes of scratch, 8-byte aligned.  area f64 [C] = sum of 0.5 |(b - a) x (c - a)|,
+ *                    volume f64 [C] = sum of a . (b x c) / 6, terms in f64 from the f32 coordinates, summed in an order the input
+ *                    fixes (no float atomics: the same input gives the same bytes); lo, hi f32 [C,3] the exact box (-0 below +0).
+ * select_count     : keep uint8 [C].  vertex_map int32 [V], face_map int32 [T]: the index a kept vertex / face gets, -1 for the
+ *                    others (bad faces and unused vertices included); counts int32 [2] = {vertices kept, faces kept}, on the device
+ * select_emit      : after select_count, with n_out_vertices, n_out_faces its counts (both >= 1): the kept vertices (and normals, unless
+ *                    NULL) and the kept faces, re-indexed, in their original relative order
+ * All return -1 without a launch for a null required pointer or a size below 1. */
+long long ngp_mesh_components_bytes(int n_faces, int n_vertices);
+int ngp_mesh_components_rounds(const int32_t* faces, int n_faces, int n_vertices, int32_t* parent, int32_t* changed, int n_rounds,
+                               void* stream);
+int ngp_mesh_components_label(const int32_t* faces, int n_faces, int n_vertices, const int32_t* parent, void* workspace,
+                              int32_t* vertex_component, int32_t* face_component, int32_t* counts /*[3]*/, void* stream);
+int ngp_mesh_components_edge_keys(const int32_t* faces, int n_faces, int n_vertices, int64_t* keys /*[3 T]*/, void* stream);
+int ngp_mesh_components_table(int n_faces, int n_vertices, const int32_t* vertex_component, const int32_t* face_component,
+                              const int64_t* sorted_keys, int n_components, int32_t* table /*[C,6]*/, void* stream);
+long long ngp_mesh_components_partial_bytes(int n_faces, int n_components);
+int ngp_mesh_components_measure(const float* vertices, const int32_t* faces, const int64_t* order, int n_faces, int n_vertices,
+                                const int32_t* face_start, const int32_t* block_start, int n_components, void* partials, double* area,
+                                double* volume, float* lo, float* hi, void* stream);
+int ngp_mesh_select_count(int n_faces, int n_vertices, const int32_t* vertex_component, const int32_t* face_component,
+                          const uint8_t* keep, int n_components, void* workspace, int32_t* vertex_map, int32_t* face_map,
+                          int32_t* counts /*[2]*/, void* stream);
+int ngp_mesh_select_emit(const float* vertices, const float* normals /* may be NULL */, const int32_t* faces, int n_faces, int n_vertices,
+                         const int32_t* vertex_map, const int32_t* face_map, int n_out_vertices, int n_out_faces, float* out_vertices,
+                         float* out_normals /* NULL iff normals is */, int32_t* out_faces, void* stream);
+
 /* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
  * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
  * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],

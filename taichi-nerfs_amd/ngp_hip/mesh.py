@@ -7,7 +7,10 @@
 
 The mesh is indexed (shared vertices), deterministic (the same grid gives the same bytes) and, wherever the surface stays off the grid
 boundary, a closed consistently oriented 2-manifold; the exact contract is in DESIGN.md section 3.  The extraction itself costs one host
-read (the vertex and face counts, to size the outputs)."""
+read (the vertex and face counts, to size the outputs).
+
+    cc = components(mesh)                              # a label per vertex and face, cc.stats: one row per piece (csrc/mesh_components.hip)
+    mesh, report = clean_mesh(mesh, keep_largest=1)    # drop the floaters"""
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -115,6 +118,109 @@ def topology(mesh):
     _, uses = np.unique(e[:, 0] * max(n_vertices, 1) + e[:, 1], return_counts=True)
     return {"vertices": n_vertices, "faces": int(len(f)), "euler": n_vertices - int(len(uses)) + int(len(f)),
             "boundary_edges": int((uses == 1).sum())}
+
+
+# ---- the pieces of a mesh (csrc/mesh_components.hip; contract: DESIGN.md section 3, "Connected components") --------------------------
+class ComponentStats(NamedTuple):
+    """One row per component, on the device."""
+    vertices: torch.Tensor                  # [C] int32
+    faces: torch.Tensor                     # [C] int32
+    edges: torch.Tensor                     # [C] int32: distinct undirected edges of good faces with three distinct indices
+    boundary_edges: torch.Tensor            # [C] int32: edges used by exactly one face
+    nonmanifold_edges: torch.Tensor         # [C] int32: edges used by three or more faces
+    euler: torch.Tensor                     # [C] int32: vertices - edges + faces
+    area: torch.Tensor                      # [C] f64: sum of 0.5 |(b - a) x (c - a)|
+    volume: torch.Tensor                    # [C] f64: sum of a . (b x c) / 6, signed; the enclosed volume of a closed, outward-oriented piece
+    lo: torch.Tensor                        # [C,3] f32: the bounding box
+    hi: torch.Tensor                        # [C,3] f32
+
+
+class MeshComponents:
+    """What components() returns.  vertex_component int32 [V] and face_component int32 [T] hold the component number (0 .. n - 1, by
+    increasing smallest vertex index) or -1 (an unused vertex, a bad face); n, bad_faces, unused_vertices and rounds are python ints.
+    .stats is the ComponentStats table, computed on first use."""
+
+    def __init__(self, vertices, faces, vertex_component, face_component, n, bad_faces, unused_vertices, rounds):
+        self.vertices, self.faces = vertices, faces
+        self.vertex_component, self.face_component = vertex_component, face_component
+        self.n, self.bad_faces, self.unused_vertices, self.rounds = n, bad_faces, unused_vertices, rounds
+        self._stats = None
+
+    @property
+    def stats(self):
+        if self._stats is None:
+            table = ops.mesh_components_table(self.faces, self.vertices.shape[0], self.vertex_component, self.face_component, self.n)
+            floats = ops.mesh_components_measure(self.vertices, self.faces, self.face_component, table[:, 1].contiguous(), self.bad_faces)
+            self._stats = ComponentStats(*[table[:, k].contiguous() for k in range(6)], *floats)
+        return self._stats
+
+
+def components(mesh, strict=True):
+    """The connected components of a Mesh or a (vertices, faces) pair of device tensors -> MeshComponents.  Two vertices are connected
+    when some face names both (vertex connectivity: two pieces that touch in one vertex are one component; connectivity through shared
+    edges only is not offered).  An unwelded file (every face with vertices of its own) falls apart into its faces: weld it first
+    (mesh_sdf.weld_vertices).  A face with an index outside [0, V) joins nothing; strict=True raises ValueError when there is one,
+    strict=False labels it -1 and counts it."""
+    vertices, faces = mesh[0], mesh[1]
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    ops._dev(vertices, torch.float32, "vertices")
+    vc, fc, counts, rounds = ops.mesh_components_label(faces, vertices.shape[0])
+    n, bad, unused = counts.tolist()                                     # the labelling's host read besides the round flags
+    if bad and strict:
+        raise ValueError("%d of the %d faces name a vertex outside 0..%d (strict=False labels them -1)" % (bad, faces.shape[0], vertices.shape[0] - 1))
+    return MeshComponents(vertices, faces, vc, fc, n, bad, unused, rounds)
+
+
+def select_components(mesh, components, keep):
+    """The sub-mesh of the components that keep (bool [C], on either device) marks -> (Mesh, vertex_map int32 [V], face_map int32 [T]).
+    Kept vertices and faces stay in their original relative order, faces are re-indexed, normals are carried; the maps hold the new
+    index or -1.  Bad faces and unused vertices are always dropped."""
+    keep = torch.as_tensor(keep)
+    if keep.dtype != torch.bool or tuple(keep.shape) != (components.n,):
+        raise ValueError("keep must be bool [%d] (one entry per component), got %s %s" % (components.n, keep.dtype, tuple(keep.shape)))
+    v, n, f, vertex_map, face_map = ops.mesh_select(mesh.vertices, mesh.normals, mesh.faces, components.vertex_component,
+                                                    components.face_component, keep.to(mesh.faces.device))
+    return Mesh(v, f, n), vertex_map, face_map
+
+
+def component_rule(faces, boundary_edges, area, volume, keep_largest=None, min_faces=0, min_area_fraction=0.0, closed_only=False, by="area"):
+    """The rule of clean_mesh on host arrays of C rows -> bool [C].  The filters first (faces >= min_faces, area >= min_area_fraction
+    of the total area, no boundary edges); then, of what is left, the keep_largest greatest by `by` ("area", "faces", "volume" = |volume|),
+    ties to the lower component number."""
+    if by not in ("area", "faces", "volume"):
+        raise ValueError('by must be "area", "faces" or "volume", got %r' % (by,))
+    if keep_largest is not None and (int(keep_largest) != keep_largest or keep_largest < 0):
+        raise ValueError("keep_largest must be None or a non-negative integer, got %r" % (keep_largest,))
+    faces, area = np.asarray(faces), np.asarray(area, np.float64)
+    keep = faces >= min_faces
+    if min_area_fraction > 0.0:
+        keep &= area >= min_area_fraction * area.sum()
+    if closed_only:
+        keep &= np.asarray(boundary_edges) == 0
+    if keep_largest is not None:
+        size = {"area": area, "faces": faces.astype(np.float64), "volume": np.abs(np.asarray(volume, np.float64))}[by]
+        ranked = [c for c in np.argsort(-size, kind="stable") if keep[c]][:int(keep_largest)]
+        keep = np.zeros(len(faces), bool)
+        keep[ranked] = True
+    return keep
+
+
+def clean_mesh(mesh, keep_largest=None, min_faces=0, min_area_fraction=0.0, closed_only=False, by="area"):
+    """Drop the floaters of a mesh -> (Mesh, report).  The rule (component_rule) is evaluated on the host from the per-component table:
+    C rows, one read.  With all defaults nothing is dropped except bad faces and unused vertices.  report: components, faces and area
+    kept and dropped, the bad faces and unused vertices found, and `kept`, the numbers of the kept components."""
+    cc = components(mesh, strict=False)
+    s = cc.stats
+    rows = torch.stack([s.faces.double(), s.boundary_edges.double(), s.area, s.volume], 1).cpu().numpy()        # the one read
+    faces, boundary, area, volume = rows[:, 0].astype(np.int64), rows[:, 1].astype(np.int64), rows[:, 2], rows[:, 3]
+    keep = component_rule(faces, boundary, area, volume, keep_largest, min_faces, min_area_fraction, closed_only, by)
+    out, _, _ = select_components(mesh, cc, torch.from_numpy(keep))
+    report = {"components_kept": int(keep.sum()), "components_dropped": int((~keep).sum()),
+              "faces_kept": int(faces[keep].sum()), "faces_dropped": int(faces[~keep].sum()),
+              "area_kept": float(area[keep].sum()), "area_dropped": float(area[~keep].sum()),
+              "bad_faces": cc.bad_faces, "unused_vertices": cc.unused_vertices, "kept": np.flatnonzero(keep).tolist()}
+    return out, report
 
 
 # ---- files (host code) -------------------------------------------------------------------------------------------------------------

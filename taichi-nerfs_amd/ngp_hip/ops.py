@@ -999,6 +999,147 @@ def mesh_winding_query(points, vertices, faces, order, moments, leaf_size=4, bet
     return winding
 
 
+# ---------------------------------------------------------------------------------------------------- connected components of a mesh
+MESH_COMPONENTS_BATCH = 4      # union-find rounds per host read of the `changed` flags
+MESH_TABLE_COLUMNS = ("vertices", "faces", "edges", "boundary_edges", "nonmanifold_edges", "euler")
+
+
+def _mesh_faces(faces, n_vertices):
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError("faces must be [T,3], got %s" % (tuple(faces.shape),))
+    n_vertices = int(n_vertices)
+    if not 0 <= n_vertices < 2**31:
+        raise ValueError("n_vertices must be in 0..2^31 - 1, got %r" % (n_vertices,))
+    _dev(faces, torch.int32, "faces")
+    return int(faces.shape[0]), n_vertices
+
+
+def _mesh_components_workspace(n_faces, n_vertices, device):
+    return torch.empty(_lib().ngp_mesh_components_bytes(n_faces, n_vertices), device=device, dtype=torch.uint8)
+
+
+def mesh_components_label(faces, n_vertices, max_rounds=None):
+    """Labels of the pieces of a mesh (csrc/mesh_components.hip): faces int32 [T,3] -> (vertex_component int32 [V], face_component int32
+    [T], counts int32 [3] = {components, bad faces, unused vertices} ON THE DEVICE, rounds).  rounds: the hook passes of the union-find
+    up to and including the first that changed nothing; the flags are read once per MESH_COMPONENTS_BATCH rounds.  More than max_rounds
+    (default V, which the scheme guarantees) raises RuntimeError."""
+    n_faces, n_vertices = _mesh_faces(faces, n_vertices)
+    dev = faces.device
+    if n_faces == 0 or n_vertices == 0:                # nothing to join: every face is bad (V = 0) or every vertex unused (T = 0)
+        counts = torch.tensor([0, n_faces, n_vertices], device=dev, dtype=torch.int32)
+        return (torch.full((n_vertices,), -1, device=dev, dtype=torch.int32), torch.full((n_faces,), -1, device=dev, dtype=torch.int32),
+                counts, 0)
+    cap = n_vertices if max_rounds is None else int(max_rounds)
+    parent = torch.arange(n_vertices, device=dev, dtype=torch.int32)
+    rounds = 0
+    while True:
+        changed = torch.zeros(MESH_COMPONENTS_BATCH, device=dev, dtype=torch.int32)
+        check(_lib().ngp_mesh_components_rounds(_ptr(faces), n_faces, n_vertices, _ptr(parent), _ptr(changed), MESH_COMPONENTS_BATCH,
+                                                _stream()), "ngp_mesh_components_rounds")
+        flags = changed.tolist()
+        if 0 in flags:
+            rounds += flags.index(0) + 1
+            break
+        rounds += MESH_COMPONENTS_BATCH
+        if rounds >= cap:
+            raise RuntimeError("the component labelling did not settle within %d rounds (the scheme guarantees V = %d)" % (cap, n_vertices))
+    if rounds > cap:
+        raise RuntimeError("the component labelling took %d rounds, more than the cap %d" % (rounds, cap))
+    workspace = _mesh_components_workspace(n_faces, n_vertices, dev)
+    vertex_component = torch.empty(n_vertices, device=dev, dtype=torch.int32)
+    face_component = torch.empty(n_faces, device=dev, dtype=torch.int32)
+    counts = torch.empty(3, device=dev, dtype=torch.int32)
+    check(_lib().ngp_mesh_components_label(_ptr(faces), n_faces, n_vertices, _ptr(parent), _ptr(workspace), _ptr(vertex_component),
+                                           _ptr(face_component), _ptr(counts), _stream()), "ngp_mesh_components_label")
+    return vertex_component, face_component, counts, rounds
+
+
+def _mesh_labels(faces, n_vertices, vertex_component, face_component):
+    n_faces, n_vertices = _mesh_faces(faces, n_vertices)
+    _dev(vertex_component, torch.int32, "vertex_component"); _dev(face_component, torch.int32, "face_component")
+    if tuple(vertex_component.shape) != (n_vertices,) or tuple(face_component.shape) != (n_faces,):
+        raise ValueError("vertex_component must be [V] and face_component [T]")
+    return n_faces, n_vertices
+
+
+def mesh_components_table(faces, n_vertices, vertex_component, face_component, n_components):
+    """The integer columns of the per-component table -> int32 [C,6] (MESH_TABLE_COLUMNS).  The 3 T edge keys are sorted by torch.sort."""
+    n_faces, n_vertices = _mesh_labels(faces, n_vertices, vertex_component, face_component)
+    n_components = int(n_components)
+    table = torch.empty(n_components, 6, device=faces.device, dtype=torch.int32)
+    if n_components == 0:
+        return table
+    keys = torch.empty(3 * n_faces, device=faces.device, dtype=torch.int64)
+    check(_lib().ngp_mesh_components_edge_keys(_ptr(faces), n_faces, n_vertices, _ptr(keys), _stream()), "ngp_mesh_components_edge_keys")
+    keys = torch.sort(keys).values
+    check(_lib().ngp_mesh_components_table(n_faces, n_vertices, _ptr(vertex_component), _ptr(face_component), _ptr(keys), n_components,
+                                           _ptr(table), _stream()), "ngp_mesh_components_table")
+    return table
+
+
+def mesh_components_measure(vertices, faces, face_component, face_counts, n_bad):
+    """Area f64 [C], signed volume f64 [C] and the box lo, hi f32 [C,3] of every component, summed in an order the input fixes.
+    face_counts int32 [C]: the table's faces column; n_bad: the number of bad faces (they sort first)."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    _dev(vertices, torch.float32, "vertices"); _dev(face_counts, torch.int32, "face_counts")
+    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
+    _dev(face_component, torch.int32, "face_component")
+    if tuple(face_component.shape) != (n_faces,):
+        raise ValueError("face_component must be [T]")
+    dev, n_components = faces.device, int(face_counts.shape[0])
+    area = torch.empty(n_components, device=dev, dtype=torch.float64)
+    volume = torch.empty(n_components, device=dev, dtype=torch.float64)
+    lo = torch.empty(n_components, 3, device=dev, dtype=torch.float32)
+    hi = torch.empty(n_components, 3, device=dev, dtype=torch.float32)
+    if n_components == 0:
+        return area, volume, lo, hi
+    order = torch.sort(face_component, stable=True).indices                      # by (component, face index): bad faces (-1) first
+    zero = torch.zeros(1, device=dev, dtype=torch.int32)
+    face_start = torch.cat([zero, torch.cumsum(face_counts, 0, dtype=torch.int32)]) + int(n_bad)
+    block_start = torch.cat([zero, torch.cumsum((face_counts + 63) // 64, 0, dtype=torch.int32)])
+    partials = torch.empty(_lib().ngp_mesh_components_partial_bytes(n_faces, n_components) // 8, device=dev, dtype=torch.float64)
+    check(_lib().ngp_mesh_components_measure(_ptr(vertices), _ptr(faces), _ptr(order), n_faces, n_vertices, _ptr(face_start),
+                                             _ptr(block_start), n_components, _ptr(partials), _ptr(area), _ptr(volume), _ptr(lo), _ptr(hi),
+                                             _stream()), "ngp_mesh_components_measure")
+    return area, volume, lo, hi
+
+
+def mesh_select(vertices, normals, faces, vertex_component, face_component, keep):
+    """The sub-mesh of the components keep (uint8 / bool [C], on the device) marks -> (vertices, normals or None, faces, vertex_map int32
+    [V], face_map int32 [T]): kept rows in their original relative order, faces re-indexed, the maps -1 for what is dropped.  One host
+    read (the two sizes); an empty selection launches no emit."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    _dev(vertices, torch.float32, "vertices")
+    n_faces, n_vertices = _mesh_labels(faces, vertices.shape[0], vertex_component, face_component)
+    if normals is not None:
+        _dev(normals, torch.float32, "normals")
+        if tuple(normals.shape) != tuple(vertices.shape):
+            raise ValueError("normals must be [V,3] like the vertices")
+    if not keep.is_cuda:
+        raise RuntimeError("keep must live on the GPU: libngp_hip has no CPU path (got device %s)" % keep.device)
+    keep = keep.to(torch.uint8).contiguous()
+    dev, n_components = faces.device, int(keep.shape[0])
+    vertex_map = torch.full((n_vertices,), -1, device=dev, dtype=torch.int32)
+    face_map = torch.full((n_faces,), -1, device=dev, dtype=torch.int32)
+    n_v = n_f = 0
+    if n_components and n_faces and n_vertices:
+        counts = torch.empty(2, device=dev, dtype=torch.int32)
+        workspace = _mesh_components_workspace(n_faces, n_vertices, dev)
+        check(_lib().ngp_mesh_select_count(n_faces, n_vertices, _ptr(vertex_component), _ptr(face_component), _ptr(keep), n_components,
+                                           _ptr(workspace), _ptr(vertex_map), _ptr(face_map), _ptr(counts), _stream()),
+              "ngp_mesh_select_count")
+        n_v, n_f = counts.tolist()                                               # the one synchronisation: the outputs' sizes
+    out_v = torch.empty(n_v, 3, device=dev, dtype=torch.float32)
+    out_n = torch.empty(n_v, 3, device=dev, dtype=torch.float32) if normals is not None else None
+    out_f = torch.empty(n_f, 3, device=dev, dtype=torch.int32)
+    if n_v and n_f:                                                              # a kept component has both; nothing kept: no launch
+        check(_lib().ngp_mesh_select_emit(_ptr(vertices), _ptr(normals), _ptr(faces), n_faces, n_vertices, _ptr(vertex_map), _ptr(face_map),
+                                          n_v, n_f, _ptr(out_v), _ptr(out_n), _ptr(out_f), _stream()), "ngp_mesh_select_emit")
+    return out_v, out_n, out_f, vertex_map, face_map
+
+
 # ---------------------------------------------------------------------------------------------------- surface rendering
 def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
     _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
