@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(1024) mse_loss_grad_kernel(const float* __rest
     float acc = 0.0f;
     for (int r = threadIdx.x; r < n_rays; r += blockDim.x) {
         const float b = bg * (1.0f - opacity[r]);
-        float go = 0.0f;
+        float go = -0.0f;                                   // -0: go is -bg * sum(gr) down to the sign of a zero (the backend turns 0 - x into -x)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float diff = (rgb[3 * r + c] + b) - target[3 * r + c];
@@ -380,7 +380,7 @@ __global__ void __launch_bounds__(256) mse_loss_grad_rays_kernel(const float* __
     if (r >= n_rays) return;
     const float k = 2.0f / (3.0f * (float)n_rays) * sf[SF_LOSS_SCALE];
     const float b = bg * (1.0f - opacity[r]);
-    float go = 0.0f, se = 0.0f;
+    float go = -0.0f, se = 0.0f;                            // (-0: see mse_loss_grad_kernel)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float diff = (rgb[3 * r + c] + b) - target[3 * r + c];
