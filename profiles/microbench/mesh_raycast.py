@@ -6,7 +6,7 @@ Meshes: the sphere (radius 0.3 in the unit box) extracted by marching tetrahedra
 profiles/microbench/mesh_sdf.py.  Rays: the 800 x 800 primary rays of a camera 1.5 from the centre that sees the whole mesh (about a
 fifth of them hit), unit directions, and 16 384 of them drawn at random; first hit and any hit, with and without the details.  Every
 time is the median (and the minimum) of --reps launches after two warm-up launches, by device events, all in this one process.
-boxes / faces per ray come from a second build of mesh_raycast.hip alone with -DNGP_MESH_RAYCAST_COUNT (two atomic counters, compiled
+boxes / faces per ray come from a second build of mesh_raycast.hip alone with -DNGP_MESH_TREE_COUNT (two atomic counters, compiled
 here into a temporary directory or given with --counting_lib; the product library has no counters).
 Comparisons on the 65^3 mesh at 16 384 rays, each labelled with what it is:
   brute_force_torch_moller_trumbore   every ray against every face, plain Moller-Trumbore in float32 torch, chunked: not watertight, not
@@ -74,7 +74,7 @@ def counting_library(tmp, prebuilt=None):
     if path is None:
         hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
         path = os.path.join(tmp, "libmesh_raycast_count.so")
-        subprocess.run([hipcc] + lib.HIPCC_FLAGS + ["-DNGP_MESH_RAYCAST_COUNT", "-Wl,-Bsymbolic", "-o", path, os.path.join(lib.CSRC, "mesh_raycast.hip")],
+        subprocess.run([hipcc] + lib.HIPCC_FLAGS + ["-DNGP_MESH_TREE_COUNT", "-Wl,-Bsymbolic", "-o", path, os.path.join(lib.CSRC, "mesh_raycast.hip")],
                        check=True)
     so = ctypes.CDLL(path)
     so.ngp_mesh_raycast.argtypes = lib.SIGNATURES["ngp_mesh_raycast"]
@@ -100,7 +100,7 @@ def main(argv=None):
     ap.add_argument("--grids", type=int, nargs="+", default=[65, 257])
     ap.add_argument("--wh", type=int, default=800)
     ap.add_argument("--no_counters", action="store_true")
-    ap.add_argument("--counting_lib", default=None, help="a prebuilt -DNGP_MESH_RAYCAST_COUNT build of mesh_raycast.hip")
+    ap.add_argument("--counting_lib", default=None, help="a prebuilt -DNGP_MESH_TREE_COUNT build of mesh_raycast.hip")
     args = ap.parse_args(argv)
     from ngp_hip import MeshSDF, ops
     from ngp_hip.mesh import extract_mesh

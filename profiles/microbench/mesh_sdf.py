@@ -7,7 +7,7 @@ Meshes: the sphere (radius 0.3 in the unit box) extracted by marching tetrahedra
 the median (and the minimum) of --reps launches after two warm-up launches, by device events, all in this one process.
 The brute force (every point against every face, the kernel's formula in torch, float32, chunked) runs on the 65^3 mesh only; for
 the 257^3 mesh its cost is stated by arithmetic from the measured pair rate.
-nodes / faces per point come from a second build of mesh_sdf.hip alone with -DNGP_MESH_SDF_COUNT (two atomic counters, compiled here
+nodes / faces per point come from a second build of mesh_sdf.hip alone with -DNGP_MESH_TREE_COUNT (two atomic counters, compiled here
 into a temporary directory; the product library has no counters).  "bytes" is arithmetic on those counters -- 24 per box tested,
 4 + 12 + 36 per face evaluated, 12 + 36 per point in and out -- i.e. the bytes REQUESTED, most of which the caches serve; the share of
 the 8 TB/s HBM roofline it would be if none were cached is given for orientation."""
@@ -77,7 +77,7 @@ def counting_library(tmp):
     from ngp_hip import lib
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     path = os.path.join(tmp, "libmesh_sdf_count.so")
-    subprocess.run([hipcc] + lib.HIPCC_FLAGS + ["-DNGP_MESH_SDF_COUNT", "-Wl,-Bsymbolic", "-o", path, os.path.join(lib.CSRC, "mesh_sdf.hip")], check=True)
+    subprocess.run([hipcc] + lib.HIPCC_FLAGS + ["-DNGP_MESH_TREE_COUNT", "-Wl,-Bsymbolic", "-o", path, os.path.join(lib.CSRC, "mesh_sdf.hip")], check=True)
     so = ctypes.CDLL(path)
     so.ngp_mesh_sdf_query.argtypes = lib.SIGNATURES["ngp_mesh_sdf_query"]
     so.ngp_mesh_sdf_counters.argtypes = [ctypes.c_void_p]

@@ -8,7 +8,7 @@ profiles/microbench/mesh_sdf.py and mesh_raycast.py.  Points: MeshSDF.sample(n, 
 Every time is the median (and the minimum) of --reps launches after two warm-up launches, by device events, all in this one process.
   moments_build        ngp_mesh_winding_build over the finished tree (one launch per level)
   queries              beta = 2 with 1 and 2 far-field terms; nodes / accepted nodes / faces per point from a second build of
-                       mesh_winding.hip alone with -DNGP_MESH_WINDING_COUNT (three atomic counters, compiled here into a temporary directory
+                       mesh_winding.hip alone with -DNGP_MESH_TREE_COUNT (three atomic counters, compiled here into a temporary directory
                        or given with --counting_lib; the product library has no counters)
 Comparisons at 16 384 points, each labelled with what it is:
   exact_sum_through_the_tree      the kernel's own beta = inf mode: every face, the built-in brute force
@@ -75,7 +75,7 @@ def counting_library(tmp, prebuilt=None):
     if path is None:
         hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
         path = os.path.join(tmp, "libmesh_winding_count.so")
-        subprocess.run([hipcc] + lib.HIPCC_FLAGS + ["-DNGP_MESH_WINDING_COUNT", "-Wl,-Bsymbolic", "-o", path, os.path.join(lib.CSRC, "mesh_winding.hip")],
+        subprocess.run([hipcc] + lib.HIPCC_FLAGS + ["-DNGP_MESH_TREE_COUNT", "-Wl,-Bsymbolic", "-o", path, os.path.join(lib.CSRC, "mesh_winding.hip")],
                        check=True)
     so = ctypes.CDLL(path)
     so.ngp_mesh_winding_query.argtypes = lib.SIGNATURES["ngp_mesh_winding_query"]
@@ -114,7 +114,7 @@ def main(argv=None):
     ap.add_argument("--no_counters", action="store_true")
     ap.add_argument("--no_reference", action="store_true", help="leave out the host-side figures of tests/mesh_winding_reference.py")
     ap.add_argument("--resources_only", action="store_true", help="no GPU: only kernel_resources and reference_beta2")
-    ap.add_argument("--counting_lib", default=None, help="a prebuilt -DNGP_MESH_WINDING_COUNT build of mesh_winding.hip")
+    ap.add_argument("--counting_lib", default=None, help="a prebuilt -DNGP_MESH_TREE_COUNT build of mesh_winding.hip")
     args = ap.parse_args(argv)
     tmp = tempfile.mkdtemp()
     result = {"kernel_resources": kernel_resources(tmp)}

@@ -47,13 +47,12 @@
 //     roundings of a slab end (p, inv, the product); 2^-21 = 8 x 2^-24 on tn and tf takes them out.
 // An inverted box fails the first comparison: padding is never entered.
 //
-// THE WALK is the stackless one of mesh_sdf.hip: sibling ((i - 1) ^ 1) + 1 and parent (i - 1) >> 1 are arithmetic, `trail` holds one bit
-// per level, no per-lane array, nothing in scratch or LDS.  Going down the lane takes the child with the smaller tn first.
-// TERMINATION.  Floats decide one thing only: whether a node is entered.  Every transition -- down to a child, across to the sibling, up
-// to the parent -- is index arithmetic on `node`, `depth` and the trail bits, each node is gone down into at most once and left
-// upwards at most once, so the walk ends after at most 3 (2 P - 1) steps for any bit pattern in rays_o and rays_d (NaN, +-inf,
-// denormals).  A ray without a dominant axis (a zero direction, or a component that is not finite) and a ray with t_min <= t_max false
-// is a miss, written without a walk.  NGP_RAYCAST_ANY_HIT leaves the walk at the first accepted face.
+// THE WALK is the one of mesh_bvh.h ("THE WALK" and "TERMINATION") with key = enter(box) for hi = min(t_max, best) and limit = +inf: the
+// child with the smaller tn first.  Its leaf loop is spelled out too, not a call of mesh_leaf_faces: through that helper (as through a
+// walk template) the compiler nests the leaf loop in another loop of the walk and 800 x 800 primary rays take a third longer
+// (profiles/mesh_tree_refactor.md).  The root is entered after its own box test.  A ray without a dominant axis (a zero direction, or
+// a component that is not finite) and a ray with t_min <= t_max false is a miss, written without a walk.  NGP_RAYCAST_ANY_HIT leaves
+// the walk after the first leaf with an accepted face.
 #include "mesh_bvh.h"
 
 namespace ngp {
@@ -130,48 +129,39 @@ __device__ __forceinline__ float mesh_ray_box(const float* __restrict__ boxes, l
     return (b[0] <= b[3] && tn <= tf && tn <= t_hi && tf >= t_lo) ? tn : INFINITY;
 }
 
-__device__ __forceinline__ MeshRayFace mesh_ray_face_at(const float* __restrict__ vertices, const int32_t* __restrict__ faces, long long f,
-                                                        const MeshRay& r, int flags) {
-    return mesh_ray_face(r, v3_load(vertices, faces[3 * f]), v3_load(vertices, faces[3 * f + 1]), v3_load(vertices, faces[3 * f + 2]), flags);
+__device__ __forceinline__ MeshRayFace mesh_ray_face_at(const MeshGeometry& g, long long f, const MeshRay& r, int flags) {
+    V3 a, b, c;
+    mesh_face_corners(g, f, a, b, c);
+    return mesh_ray_face(r, a, b, c, flags);
 }
 
-#ifdef NGP_MESH_RAYCAST_COUNT
-__device__ unsigned long long mesh_raycast_counters[2];      // boxes tested, faces tested: the microbenchmark's build only
-#endif
-
 __global__ void __launch_bounds__(MESH_RAYCAST_BLOCK) mesh_raycast_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int n,
-                                                                          const float* __restrict__ vertices, const int32_t* __restrict__ faces,
-                                                                          const int32_t* __restrict__ order, const float* __restrict__ boxes,
-                                                                          int n_faces, int leaf_size, int padded, float t_min, float t_max,
-                                                                          int flags, float* __restrict__ t_out, int32_t* __restrict__ face_out,
-                                                                          float* __restrict__ bary, int32_t* __restrict__ side) {
+                                                                          MeshGeometry g, const float* __restrict__ boxes, float t_min,
+                                                                          float t_max, int flags, float* __restrict__ t_out,
+                                                                          int32_t* __restrict__ face_out, float* __restrict__ bary,
+                                                                          int32_t* __restrict__ side) {
     const long long i = (long long)blockIdx.x * MESH_RAYCAST_BLOCK + threadIdx.x;
     if (i >= n) return;
     MeshRay ray;
     float best = INFINITY;
     int best_pos = -1;
-#ifdef NGP_MESH_RAYCAST_COUNT
-    unsigned long long n_nodes = 0, n_tris = 0;
-#endif
+    MeshTally<2> tally;                      // boxes tested, faces tested
     if (mesh_ray_setup(v3_load(rays_o, i), v3_load(rays_d, i), ray) && t_min <= t_max) {
-        const int first_leaf = padded - 1;
+        // mesh_bvh.h, "THE WALK": keep this and mesh_sdf_query_kernel's alike, state for state
+        const int first_leaf = g.padded - 1;
         const bool any_hit = (flags & NGP_RAYCAST_ANY_HIT) != 0;
         int node = 0, depth = 0;
         uint32_t trail = 0;
         bool down = mesh_ray_box(boxes, 0, ray, t_min, t_max) < INFINITY;
-#ifdef NGP_MESH_RAYCAST_COUNT
-        ++n_nodes;
-#endif
+        tally.add(0);
         for (;;) {
             if (down) {
                 if (node >= first_leaf) {
-                    const long long s0 = (long long)(node - first_leaf) * leaf_size;
-                    for (int j = 0; j < leaf_size && s0 + j < n_faces; ++j) {
-                        const float t = mesh_ray_face_at(vertices, faces, order[s0 + j], ray, flags).t;
+                    const long long s0 = (long long)(node - first_leaf) * g.leaf_size;
+                    for (int j = 0; j < g.leaf_size && s0 + j < g.n_faces; ++j) {
+                        const float t = mesh_ray_face_at(g, g.order[s0 + j], ray, flags).t;
                         if (t_min <= t && t <= t_max && t < best) { best = t; best_pos = (int)(s0 + j); }
-#ifdef NGP_MESH_RAYCAST_COUNT
-                        ++n_tris;
-#endif
+                        tally.add(1);
                     }
                     if (any_hit && best_pos >= 0) break;
                     down = false;
@@ -179,9 +169,7 @@ __global__ void __launch_bounds__(MESH_RAYCAST_BLOCK) mesh_raycast_kernel(const 
                     const int c0 = 2 * node + 1;
                     const float hi = fminf(t_max, best);
                     const float e0 = mesh_ray_box(boxes, c0, ray, t_min, hi), e1 = mesh_ray_box(boxes, c0 + 1, ray, t_min, hi);
-#ifdef NGP_MESH_RAYCAST_COUNT
-                    n_nodes += 2;
-#endif
+                    tally.add(0, 2);
                     if (fminf(e0, e1) < INFINITY) {
                         node = e1 < e0 ? c0 + 1 : c0;
                         ++depth;
@@ -195,9 +183,7 @@ __global__ void __launch_bounds__(MESH_RAYCAST_BLOCK) mesh_raycast_kernel(const 
                 if (!((trail >> depth) & 1u)) {
                     trail |= 1u << depth;
                     node = ((node - 1) ^ 1) + 1;
-#ifdef NGP_MESH_RAYCAST_COUNT
-                    ++n_nodes;
-#endif
+                    tally.add(0);
                     down = mesh_ray_box(boxes, node, ray, t_min, fminf(t_max, best)) < INFINITY;
                 } else {
                     node = (node - 1) >> 1;
@@ -206,10 +192,7 @@ __global__ void __launch_bounds__(MESH_RAYCAST_BLOCK) mesh_raycast_kernel(const 
             }
         }
     }
-#ifdef NGP_MESH_RAYCAST_COUNT
-    atomicAdd(&mesh_raycast_counters[0], n_nodes);
-    atomicAdd(&mesh_raycast_counters[1], n_tris);
-#endif
+    tally.flush();
     t_out[i] = best;
     if (best_pos < 0) {
         if (face_out) face_out[i] = -1;
@@ -218,8 +201,8 @@ __global__ void __launch_bounds__(MESH_RAYCAST_BLOCK) mesh_raycast_kernel(const 
         return;
     }
     if (!face_out && !bary && !side) return;
-    const long long f = order[best_pos];
-    const MeshRayFace h = mesh_ray_face_at(vertices, faces, f, ray, flags);       // the same bits as in the walk
+    const long long f = g.order[best_pos];
+    const MeshRayFace h = mesh_ray_face_at(g, f, ray, flags);       // the same bits as in the walk
     if (face_out) face_out[i] = (int32_t)f;
     if (bary) { bary[2 * i] = h.v; bary[2 * i + 1] = h.w; }
     if (side) side[i] = h.det > 0.0f ? 1 : -1;
@@ -234,25 +217,20 @@ extern "C" {
 int ngp_mesh_raycast(const float* rays_o, const float* rays_d, int n, const float* vertices, const int32_t* faces, const int32_t* order,
                      const float* boxes, int n_faces, int leaf_size, float t_min, float t_max, int flags, float* t, int32_t* face,
                      float* bary, int32_t* side, void* stream) {
+    MeshGeometry g;
     MeshTree tree;
-    if (!vertices || !faces || !order || !boxes || n < 0 || (flags & ~MESH_RAYCAST_FLAGS) || !mesh_tree(n_faces, leaf_size, tree)) return -1;
+    if (!boxes || n < 0 || (flags & ~MESH_RAYCAST_FLAGS) || !mesh_geometry(vertices, faces, order, n_faces, leaf_size, g, tree)) return -1;
     if (n == 0) return 0;                    // an empty batch has no rays and no outputs: their pointers may be null
     if (!rays_o || !rays_d || !t) return -1;
     hipLaunchKernelGGL(mesh_raycast_kernel, dim3((unsigned)(((long long)n + MESH_RAYCAST_BLOCK - 1) / MESH_RAYCAST_BLOCK)),
-                       dim3(MESH_RAYCAST_BLOCK), 0, (hipStream_t)stream, rays_o, rays_d, n, vertices, faces, order, boxes, n_faces,
-                       leaf_size, (int)tree.padded, t_min, t_max, flags, t, face, bary, side);
+                       dim3(MESH_RAYCAST_BLOCK), 0, (hipStream_t)stream, rays_o, rays_d, n, g, boxes, t_min, t_max, flags, t, face, bary,
+                       side);
     NGP_LAUNCH_CHECK();
     return 0;
 }
 
-#ifdef NGP_MESH_RAYCAST_COUNT
-// the microbenchmark's build only (profiles/microbench/mesh_raycast.py binds it by hand): read and clear the two counters
-int ngp_mesh_raycast_counters(unsigned long long* out) {
-    const unsigned long long zero[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(mesh_raycast_counters), sizeof(zero));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(mesh_raycast_counters), zero, sizeof(zero));
-    return -(int)e;
-}
-#endif
+// the microbenchmark's build only (profiles/microbench/mesh_raycast.py binds it by hand): read and clear the two tallies of MeshRayFirst
+NGP_MESH_TALLY_ENTRY(ngp_mesh_raycast_counters, 2)
 
 }  // extern "C"
+

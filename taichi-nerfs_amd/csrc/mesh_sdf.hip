@@ -43,10 +43,8 @@
 //     takes out these, the 2 x 3 x 2^-24 of the face's side of the comparison and the three roundings of r.r.
 // An inverted box gives lb = +inf, which is never < best (best starts at +inf): padding is never entered.
 //
-// THE WALK is stackless: the tree is implicit, so sibling ((i - 1) ^ 1) + 1 and parent (i - 1) >> 1 are arithmetic, and one bit per level
-// (`trail`, bit d = at depth d the second of the two children has been taken) replaces the stack -- no per-lane array, nothing in scratch
-// or LDS.  Going down the lane takes the nearer child first (smaller lb), so best tightens early; coming back up it tests the sibling's box
-// again (one 24-byte read instead of a stored bound).  Depth <= MESH_SDF_MAX_DEPTH = 24 (2^24 leaves), the entries refuse more.
+// THE WALK is the one of mesh_bvh.h ("THE WALK" and "TERMINATION") with key = lb and limit = best: the nearer child first.  The root is
+// entered without a test: a tree has at least one face.
 //
 // THE SIGN (signed mode: both normal arrays given): s = +1 if n.r >= 0 else -1, n by the feature of the winning face f -- interior:
 // cross(ab, ac), unnormalised; edge e: edge_normals[f, e]; vertex k: vertex_normals[faces[f, k]] (the angle-weighted pseudonormals of
@@ -60,41 +58,32 @@ constexpr int MESH_SDF_QUERY_BLOCK = 64;                        // one wave per 
 constexpr float MESH_SDF_WIDEN = 1.0f / 262144.0f;             // 2^-18: of the leaf box's longest side
 constexpr float MESH_SDF_DEFLATE = 1.0f - 1.0f / 262144.0f;    // 1 - 2^-18: on the squared lower bound
 
-__global__ void __launch_bounds__(256) mesh_sdf_leaf_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
-                                                            const int32_t* __restrict__ order, int n_faces, int leaf_size, int padded,
-                                                            float* __restrict__ boxes) {
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= padded) return;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    const long long first = k * leaf_size;
-    for (int j = 0; j < leaf_size && first + j < n_faces; ++j) {
-        const long long f = order[first + j];
-        for (int c = 0; c < 3; ++c) {
-            const long long v = faces[3 * f + c];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float x = vertices[3 * v + a];
-                lo[a] = fminf(lo[a], x);
-                hi[a] = fmaxf(hi[a], x);
-            }
-        }
+__global__ void __launch_bounds__(MESH_SWEEP_BLOCK) mesh_sdf_leaf_kernel(MeshGeometry g, float* __restrict__ boxes) {
+    const long long k = (long long)blockIdx.x * MESH_SWEEP_BLOCK + threadIdx.x;
+    if (k >= g.padded) return;
+    V3 lo = {INFINITY, INFINITY, INFINITY}, hi = {-INFINITY, -INFINITY, -INFINITY};
+    const auto grow = [&](V3 v) {
+        lo = {fminf(lo.x, v.x), fminf(lo.y, v.y), fminf(lo.z, v.z)};
+        hi = {fmaxf(hi.x, v.x), fmaxf(hi.y, v.y), fmaxf(hi.z, v.z)};
+    };
+    mesh_leaf_faces(g, k, [&](long long, long long f) {
+        V3 a, b, c;
+        mesh_face_corners(g, f, a, b, c);
+        grow(a); grow(b); grow(c);
+    });
+    if (k * g.leaf_size < g.n_faces) {
+        const float m = fmaxf(fmaxf(hi.x - lo.x, hi.y - lo.y), hi.z - lo.z) * MESH_SDF_WIDEN;
+        lo = {nextafterf(lo.x - m, -INFINITY), nextafterf(lo.y - m, -INFINITY), nextafterf(lo.z - m, -INFINITY)};
+        hi = {nextafterf(hi.x + m, INFINITY), nextafterf(hi.y + m, INFINITY), nextafterf(hi.z + m, INFINITY)};
     }
-    if (first < n_faces) {
-        const float m = fmaxf(fmaxf(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]) * MESH_SDF_WIDEN;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = nextafterf(lo[a] - m, -INFINITY);
-            hi[a] = nextafterf(hi[a] + m, INFINITY);
-        }
-    }
-    float* out = boxes + 6 * ((long long)padded - 1 + k);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { out[a] = lo[a]; out[3 + a] = hi[a]; }
+    float* out = boxes + 6 * ((long long)g.padded - 1 + k);
+    out[0] = lo.x; out[1] = lo.y; out[2] = lo.z;
+    out[3] = hi.x; out[4] = hi.y; out[5] = hi.z;
 }
 
 // nodes [first, first + count) of one level: the union of the children
-__global__ void __launch_bounds__(256) mesh_sdf_level_kernel(float* __restrict__ boxes, int first, int count) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+__global__ void __launch_bounds__(MESH_SWEEP_BLOCK) mesh_sdf_level_kernel(float* __restrict__ boxes, int first, int count) {
+    const long long t = (long long)blockIdx.x * MESH_SWEEP_BLOCK + threadIdx.x;
     if (t >= count) return;
     const long long i = first + t;
     const float* l = boxes + 6 * (2 * i + 1);
@@ -130,7 +119,7 @@ __device__ __forceinline__ MeshHit mesh_closest(V3 p, V3 a, V3 b, V3 c) {
     h.feature = feature;
     h.closest = {(a.x + ab.x * v) + ac.x * w, (a.y + ab.y * v) + ac.y * w, (a.z + ab.z * v) + ac.z * w};
     h.r = {ap.x - (ab.x * v + ac.x * w), ap.y - (ab.y * v + ac.y * w), ap.z - (ab.z * v + ac.z * w)};
-    h.n = {ab.y * ac.z - ab.z * ac.y, ab.z * ac.x - ab.x * ac.z, ab.x * ac.y - ab.y * ac.x};
+    h.n = v3_cross(ab, ac);
     h.d2 = (h.n.x != 0.0f || h.n.y != 0.0f || h.n.z != 0.0f) ? v3_dot(h.r, h.r) : NAN;       // no area, no normal: not a face
     return h;
 }
@@ -142,13 +131,11 @@ __device__ __forceinline__ float mesh_box_bound(const float* __restrict__ boxes,
     return ((gx * gx + gy * gy) + gz * gz) * MESH_SDF_DEFLATE;
 }
 
+// (vertices, faces) loose, not a MeshGeometry, and the corner loads spelled out: mesh_sdf_query_kernel keeps the parent's parameters and
+// text so that it compiles to the same instructions (profiles/mesh_tree_refactor.md)
 __device__ __forceinline__ MeshHit mesh_face_hit(const float* __restrict__ vertices, const int32_t* __restrict__ faces, long long f, V3 p) {
     return mesh_closest(p, v3_load(vertices, faces[3 * f]), v3_load(vertices, faces[3 * f + 1]), v3_load(vertices, faces[3 * f + 2]));
 }
-
-#ifdef NGP_MESH_SDF_COUNT
-__device__ unsigned long long mesh_sdf_counters[2];          // nodes whose box was tested, faces evaluated: the microbenchmark's build only
-#endif
 
 __global__ void __launch_bounds__(MESH_SDF_QUERY_BLOCK) mesh_sdf_query_kernel(const float* __restrict__ points, int n, const float* __restrict__ vertices,
                                                              const int32_t* __restrict__ faces, const int32_t* __restrict__ order,
@@ -162,30 +149,24 @@ __global__ void __launch_bounds__(MESH_SDF_QUERY_BLOCK) mesh_sdf_query_kernel(co
     const int first_leaf = padded - 1;
     float best = INFINITY;
     int best_pos = -1;
+    MeshTally<2> tally;                      // boxes tested, faces evaluated
     int node = 0, depth = 0;
     uint32_t trail = 0;
     bool down = true;                        // the root is entered without a test: a tree has at least one face
-#ifdef NGP_MESH_SDF_COUNT
-    unsigned long long n_nodes = 0, n_tris = 0;
-#endif
-    for (;;) {
+    for (;;) {                               // mesh_bvh.h, "THE WALK": keep this and mesh_raycast_kernel's alike, state for state
         if (down) {
             if (node >= first_leaf) {
                 const long long s0 = (long long)(node - first_leaf) * leaf_size;
                 for (int j = 0; j < leaf_size && s0 + j < n_faces; ++j) {
                     const MeshHit h = mesh_face_hit(vertices, faces, order[s0 + j], p);
                     if (h.d2 < best) { best = h.d2; best_pos = (int)(s0 + j); }
-#ifdef NGP_MESH_SDF_COUNT
-                    ++n_tris;
-#endif
+                    tally.add(1);
                 }
                 down = false;
             } else {
                 const int c0 = 2 * node + 1;
                 const float l0 = mesh_box_bound(boxes, c0, p), l1 = mesh_box_bound(boxes, c0 + 1, p);
-#ifdef NGP_MESH_SDF_COUNT
-                n_nodes += 2;
-#endif
+                tally.add(0, 2);
                 if (fminf(l0, l1) < best) {
                     node = l1 < l0 ? c0 + 1 : c0;
                     ++depth;
@@ -199,9 +180,7 @@ __global__ void __launch_bounds__(MESH_SDF_QUERY_BLOCK) mesh_sdf_query_kernel(co
             if (!((trail >> depth) & 1u)) {
                 trail |= 1u << depth;
                 node = ((node - 1) ^ 1) + 1;
-#ifdef NGP_MESH_SDF_COUNT
-                ++n_nodes;
-#endif
+                tally.add(0);
                 down = mesh_box_bound(boxes, node, p) < best;
             } else {
                 node = (node - 1) >> 1;
@@ -209,10 +188,7 @@ __global__ void __launch_bounds__(MESH_SDF_QUERY_BLOCK) mesh_sdf_query_kernel(co
             }
         }
     }
-#ifdef NGP_MESH_SDF_COUNT
-    atomicAdd(&mesh_sdf_counters[0], n_nodes);
-    atomicAdd(&mesh_sdf_counters[1], n_tris);
-#endif
+    tally.flush();
     if (best_pos < 0) {                      // every face evaluated to NaN: no nearest face
         sdf[i] = INFINITY;
         if (closest) { closest[3 * i] = p.x; closest[3 * i + 1] = p.y; closest[3 * i + 2] = p.z; }
@@ -221,7 +197,7 @@ __global__ void __launch_bounds__(MESH_SDF_QUERY_BLOCK) mesh_sdf_query_kernel(co
         return;
     }
     const long long f = order[best_pos];
-    const MeshHit h = mesh_face_hit(vertices, faces, f, p);       // the same bits as in the walk
+    const MeshHit h = mesh_face_hit(vertices, faces, f, p);                    // the same bits as in the walk
     float s = 1.0f;
     if (edge_normals) {
         V3 nrm = h.n;
@@ -249,16 +225,15 @@ long long ngp_mesh_bvh_bytes(long long n_faces, int leaf_size) {
 
 int ngp_mesh_bvh_build(const float* vertices, const int32_t* faces, const int32_t* order, int n_faces, int leaf_size, float* boxes,
                        void* stream) {
+    MeshGeometry g;
     MeshTree t;
-    if (!vertices || !faces || !order || !boxes || !mesh_tree(n_faces, leaf_size, t)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    const int padded = (int)t.padded;
-    hipLaunchKernelGGL(mesh_sdf_leaf_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, s, vertices, faces, order, n_faces,
-                       leaf_size, padded, boxes);
-    for (int d = t.depth - 1; d >= 0; --d) {
-        const int count = 1 << d;
-        hipLaunchKernelGGL(mesh_sdf_level_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, boxes, count - 1, count);
-    }
+    if (!boxes || !mesh_geometry(vertices, faces, order, n_faces, leaf_size, g, t)) return -1;
+    mesh_tree_sweep(
+        t, (hipStream_t)stream,
+        [&](dim3 grid, dim3 block, hipStream_t s) { hipLaunchKernelGGL(mesh_sdf_leaf_kernel, grid, block, 0, s, g, boxes); },
+        [&](dim3 grid, dim3 block, hipStream_t s, int first, int count) {
+            hipLaunchKernelGGL(mesh_sdf_level_kernel, grid, block, 0, s, boxes, first, count);
+        });
     NGP_LAUNCH_CHECK();
     return 0;
 }
@@ -266,27 +241,20 @@ int ngp_mesh_bvh_build(const float* vertices, const int32_t* faces, const int32_
 int ngp_mesh_sdf_query(const float* points, int n, const float* vertices, const int32_t* faces, const int32_t* order, const float* boxes,
                        int n_faces, int leaf_size, const float* edge_normals, const float* vertex_normals, float* sdf, float* closest,
                        int32_t* face, int32_t* feature, void* stream) {
+    MeshGeometry g;
     MeshTree t;
-    if (!vertices || !faces || !order || !boxes || n < 0 || !mesh_tree(n_faces, leaf_size, t)) return -1;
+    if (!boxes || n < 0 || !mesh_geometry(vertices, faces, order, n_faces, leaf_size, g, t)) return -1;
     if ((edge_normals == nullptr) != (vertex_normals == nullptr)) return -1;
     if (n == 0) return 0;                    // an empty batch has no points and no outputs: their pointers may be null
     if (!points || !sdf) return -1;
     hipLaunchKernelGGL(mesh_sdf_query_kernel, dim3((unsigned)(((long long)n + MESH_SDF_QUERY_BLOCK - 1) / MESH_SDF_QUERY_BLOCK)),
-                       dim3(MESH_SDF_QUERY_BLOCK), 0, (hipStream_t)stream, points, n,
-                       vertices, faces, order, boxes, n_faces, leaf_size, (int)t.padded, edge_normals, vertex_normals, sdf, closest, face,
-                       feature);
+                       dim3(MESH_SDF_QUERY_BLOCK), 0, (hipStream_t)stream, points, n, g.vertices, g.faces, g.order, boxes, g.n_faces,
+                       g.leaf_size, g.padded, edge_normals, vertex_normals, sdf, closest, face, feature);
     NGP_LAUNCH_CHECK();
     return 0;
 }
 
-#ifdef NGP_MESH_SDF_COUNT
-// the microbenchmark's build only (profiles/microbench/mesh_sdf.py binds it by hand): read and clear the two counters
-int ngp_mesh_sdf_counters(unsigned long long* out) {
-    const unsigned long long zero[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(mesh_sdf_counters), sizeof(zero));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(mesh_sdf_counters), zero, sizeof(zero));
-    return -(int)e;
-}
-#endif
+// the microbenchmark's build only (profiles/microbench/mesh_sdf.py binds it by hand): read and clear the two tallies
+NGP_MESH_TALLY_ENTRY(ngp_mesh_sdf_counters, 2)
 
 }  // extern "C"

@@ -61,10 +61,6 @@ constexpr int MESH_WINDING_ROW = 20;                            // floats per no
 constexpr float MESH_WINDING_ROUND_UP = 1.0f + 1.0f / 2097152.0f;      // 1 + 2^-21: on the radius
 constexpr float MESH_WINDING_INV_4PI = 0.07957747154594767f;
 
-__device__ __forceinline__ V3 v3_add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 v3_scale(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 v3_cross(V3 u, V3 v) { return {u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x}; }
-
 struct MeshMoments { V3 p; float r; V3 n; float area; float t[9]; };
 
 __device__ __forceinline__ MeshMoments mesh_moments_load(const float* __restrict__ row) {
@@ -102,25 +98,24 @@ __device__ __forceinline__ float mesh_box_radius(const float* __restrict__ box, 
     return sqrtf(v3_dot(m, m)) * MESH_WINDING_ROUND_UP;
 }
 
-__global__ void __launch_bounds__(256) mesh_winding_leaf_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
-                                                                const int32_t* __restrict__ order, const float* __restrict__ boxes,
-                                                                int n_faces, int leaf_size, int padded, float* __restrict__ moments) {
-    const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (k >= padded) return;
-    const long long node = (long long)padded - 1 + k;
+__global__ void __launch_bounds__(MESH_SWEEP_BLOCK) mesh_winding_leaf_kernel(MeshGeometry g, const float* __restrict__ boxes,
+                                                                             float* __restrict__ moments) {
+    const long long k = (long long)blockIdx.x * MESH_SWEEP_BLOCK + threadIdx.x;
+    if (k >= g.padded) return;
+    const long long node = (long long)g.padded - 1 + k;
     float* row = moments + MESH_WINDING_ROW * node;
-    const long long first = k * leaf_size;
-    if (first >= n_faces) { mesh_moments_store_empty(row); return; }
-    const V3 o = v3_load(vertices, faces[3 * (long long)order[first]]);
+    const long long first = k * g.leaf_size;
+    if (first >= g.n_faces) { mesh_moments_store_empty(row); return; }
+    const V3 o = v3_load(g.vertices, g.faces[3 * (long long)g.order[first]]);
     MeshMoments m;
     m.area = 0.0f;
     m.n = {0.0f, 0.0f, 0.0f};
     V3 s = {0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int i = 0; i < 9; ++i) m.t[i] = 0.0f;
-    for (int j = 0; j < leaf_size && first + j < n_faces; ++j) {
-        const long long f = order[first + j];
-        const V3 a = v3_load(vertices, faces[3 * f]), b = v3_load(vertices, faces[3 * f + 1]), c = v3_load(vertices, faces[3 * f + 2]);
+    mesh_leaf_faces(g, k, [&](long long, long long f) {
+        V3 a, b, c;
+        mesh_face_corners(g, f, a, b, c);
         const V3 n2 = v3_cross(v3_sub(b, a), v3_sub(c, a));
         const V3 an = v3_scale(n2, 0.5f);
         const float area = 0.5f * sqrtf(v3_dot(n2, n2));
@@ -132,7 +127,7 @@ __global__ void __launch_bounds__(256) mesh_winding_leaf_kernel(const float* __r
         m.t[0] += cf.x * an.x; m.t[1] += cf.x * an.y; m.t[2] += cf.x * an.z;
         m.t[3] += cf.y * an.x; m.t[4] += cf.y * an.y; m.t[5] += cf.y * an.z;
         m.t[6] += cf.z * an.x; m.t[7] += cf.z * an.y; m.t[8] += cf.z * an.z;
-    }
+    });
     const float* box = boxes + 6 * node;
     V3 pl;
     if (m.area > 0.0f) {
@@ -150,8 +145,9 @@ __global__ void __launch_bounds__(256) mesh_winding_leaf_kernel(const float* __r
 }
 
 // nodes [first, first + count) of one level: the children's moments moved to the common centroid and added
-__global__ void __launch_bounds__(256) mesh_winding_level_kernel(const float* __restrict__ boxes, float* moments, int first, int count) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+__global__ void __launch_bounds__(MESH_SWEEP_BLOCK) mesh_winding_level_kernel(const float* __restrict__ boxes, float* moments, int first,
+                                                                              int count) {
+    const long long t = (long long)blockIdx.x * MESH_SWEEP_BLOCK + threadIdx.x;
     if (t >= count) return;
     const long long i = first + t;
     float* row = moments + MESH_WINDING_ROW * i;
@@ -212,53 +208,36 @@ __device__ __forceinline__ float mesh_far_field(const float4* __restrict__ row, 
     return term;
 }
 
-#ifdef NGP_MESH_WINDING_COUNT
-__device__ unsigned long long mesh_winding_counters[3];      // nodes tested, nodes accepted, faces evaluated: the microbenchmark's build only
-#endif
-
 template <int ORDER>
-__global__ void __launch_bounds__(MESH_WINDING_BLOCK) mesh_winding_query_kernel(const float* __restrict__ points, int n,
-                                                                                const float* __restrict__ vertices,
-                                                                                const int32_t* __restrict__ faces,
-                                                                                const int32_t* __restrict__ order,
-                                                                                const float4* __restrict__ moments, int n_faces,
-                                                                                int leaf_size, int padded, float beta,
+__global__ void __launch_bounds__(MESH_WINDING_BLOCK) mesh_winding_query_kernel(const float* __restrict__ points, int n, MeshGeometry g,
+                                                                                const float4* __restrict__ moments, float beta,
                                                                                 float* __restrict__ winding) {
     const long long i = (long long)blockIdx.x * MESH_WINDING_BLOCK + threadIdx.x;
     if (i >= n) return;
     const V3 q = v3_load(points, i);
     const float big = 3.402823466e+38f;
     if (!(fabsf(q.x) <= big && fabsf(q.y) <= big && fabsf(q.z) <= big)) { winding[i] = NAN; return; }
-    const int first_leaf = padded - 1;
+    const int first_leaf = g.padded - 1;
     float sum = 0.0f;
     int node = 0;
-#ifdef NGP_MESH_WINDING_COUNT
-    unsigned long long n_nodes = 0, n_accepted = 0, n_tris = 0;
-#endif
+    MeshTally<3> tally;                                               // nodes tested, nodes accepted, faces evaluated
     for (;;) {
         const float4* row = moments + 5 * (long long)node;
         const float4 m0 = row[0];                                     // p, r
-#ifdef NGP_MESH_WINDING_COUNT
-        ++n_nodes;
-#endif
+        tally.add(0);
         if (m0.w >= 0.0f) {                                           // a node with faces
             const V3 d = v3_sub(V3{m0.x, m0.y, m0.z}, q);
             const float d2 = v3_dot(d, d), br = beta * m0.w;
             if (d2 > br * br) {
                 sum += mesh_far_field<ORDER>(row, d, d2);
-#ifdef NGP_MESH_WINDING_COUNT
-                ++n_accepted;
-#endif
+                tally.add(1);
             } else if (node >= first_leaf) {
-                const long long s0 = (long long)(node - first_leaf) * leaf_size;
-                for (int j = 0; j < leaf_size && s0 + j < n_faces; ++j) {
-                    const long long f = order[s0 + j];
-                    sum += mesh_solid_angle(q, v3_load(vertices, faces[3 * f]), v3_load(vertices, faces[3 * f + 1]),
-                                            v3_load(vertices, faces[3 * f + 2]));
-#ifdef NGP_MESH_WINDING_COUNT
-                    ++n_tris;
-#endif
-                }
+                mesh_leaf_faces(g, node - first_leaf, [&](long long, long long f) {
+                    V3 a, b, c;
+                    mesh_face_corners(g, f, a, b, c);
+                    sum += mesh_solid_angle(q, a, b, c);
+                    tally.add(2);
+                });
             } else {
                 node = 2 * node + 1;
                 continue;
@@ -268,11 +247,7 @@ __global__ void __launch_bounds__(MESH_WINDING_BLOCK) mesh_winding_query_kernel(
         if (node == 0) break;
         ++node;                                                       // a left child: across to the sibling
     }
-#ifdef NGP_MESH_WINDING_COUNT
-    atomicAdd(&mesh_winding_counters[0], n_nodes);
-    atomicAdd(&mesh_winding_counters[1], n_accepted);
-    atomicAdd(&mesh_winding_counters[2], n_tris);
-#endif
+    tally.flush();
     winding[i] = sum * MESH_WINDING_INV_4PI;
 }
 
@@ -290,48 +265,39 @@ long long ngp_mesh_winding_bytes(long long n_faces, int leaf_size) {
 
 int ngp_mesh_winding_build(const float* vertices, const int32_t* faces, const int32_t* order, const float* boxes, int n_faces,
                            int leaf_size, float* moments, void* stream) {
+    MeshGeometry g;
     MeshTree t;
-    if (!vertices || !faces || !order || !boxes || !moments || !mesh_tree(n_faces, leaf_size, t)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    const int padded = (int)t.padded;
-    hipLaunchKernelGGL(mesh_winding_leaf_kernel, dim3((unsigned)((padded + 255) / 256)), dim3(256), 0, s, vertices, faces, order, boxes,
-                       n_faces, leaf_size, padded, moments);
-    for (int d = t.depth - 1; d >= 0; --d) {
-        const int count = 1 << d;
-        hipLaunchKernelGGL(mesh_winding_level_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, boxes, moments, count - 1,
-                           count);
-    }
+    if (!boxes || !moments || !mesh_geometry(vertices, faces, order, n_faces, leaf_size, g, t)) return -1;
+    mesh_tree_sweep(
+        t, (hipStream_t)stream,
+        [&](dim3 grid, dim3 block, hipStream_t s) { hipLaunchKernelGGL(mesh_winding_leaf_kernel, grid, block, 0, s, g, boxes, moments); },
+        [&](dim3 grid, dim3 block, hipStream_t s, int first, int count) {
+            hipLaunchKernelGGL(mesh_winding_level_kernel, grid, block, 0, s, boxes, moments, first, count);
+        });
     NGP_LAUNCH_CHECK();
     return 0;
 }
 
 int ngp_mesh_winding_query(const float* points, int n, const float* vertices, const int32_t* faces, const int32_t* order,
                            const float* moments, int n_faces, int leaf_size, float beta, int order_terms, float* winding, void* stream) {
+    MeshGeometry g;
     MeshTree t;
-    if (!vertices || !faces || !order || !moments || n < 0 || !mesh_tree(n_faces, leaf_size, t)) return -1;
+    if (!moments || n < 0 || !mesh_geometry(vertices, faces, order, n_faces, leaf_size, g, t)) return -1;
     if (!(beta >= 1.0f) || (order_terms != 1 && order_terms != 2)) return -1;      // a NaN beta fails the comparison too
     if (n == 0) return 0;                    // an empty batch has no points and no output: their pointers may be null
     if (!points || !winding) return -1;
     const dim3 grid((unsigned)(((long long)n + MESH_WINDING_BLOCK - 1) / MESH_WINDING_BLOCK)), block(MESH_WINDING_BLOCK);
     const float4* rows = (const float4*)moments;
     if (order_terms == 1)
-        hipLaunchKernelGGL(mesh_winding_query_kernel<1>, grid, block, 0, (hipStream_t)stream, points, n, vertices, faces, order, rows,
-                           n_faces, leaf_size, (int)t.padded, beta, winding);
+        hipLaunchKernelGGL(mesh_winding_query_kernel<1>, grid, block, 0, (hipStream_t)stream, points, n, g, rows, beta, winding);
     else
-        hipLaunchKernelGGL(mesh_winding_query_kernel<2>, grid, block, 0, (hipStream_t)stream, points, n, vertices, faces, order, rows,
-                           n_faces, leaf_size, (int)t.padded, beta, winding);
+        hipLaunchKernelGGL(mesh_winding_query_kernel<2>, grid, block, 0, (hipStream_t)stream, points, n, g, rows, beta, winding);
     NGP_LAUNCH_CHECK();
     return 0;
 }
 
-#ifdef NGP_MESH_WINDING_COUNT
-// the microbenchmark's build only (profiles/microbench/mesh_winding.py binds it by hand): read and clear the three counters
-int ngp_mesh_winding_counters(unsigned long long* out) {
-    const unsigned long long zero[3] = {0, 0, 0};
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(mesh_winding_counters), sizeof(zero));
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(mesh_winding_counters), zero, sizeof(zero));
-    return -(int)e;
-}
-#endif
+// the microbenchmark's build only (profiles/microbench/mesh_winding.py binds it by hand): read and clear the three tallies
+NGP_MESH_TALLY_ENTRY(ngp_mesh_winding_counters, 3)
 
 }  // extern "C"
+

@@ -868,8 +868,9 @@ def mesh_emit(values, iso, sign, lo, h, workspace, n_vertices, n_faces, normals=
 MESH_SDF_MAX_LEAF = _lib_mod._ABI.defines["NGP_MESH_SDF_MAX_LEAF"]
 
 
-def _mesh_sdf_mesh(vertices, faces, order, leaf_size):
-    """Shapes first (no device needed), then the devices -> (n_faces in the tree, bytes of its boxes)."""
+def _mesh_sdf_mesh(vertices, faces, order, leaf_size, boxes=None):
+    """Shapes first (no device needed), then the devices -> (n_faces in the tree, bytes of its boxes); boxes, where given, must be that
+    tree's."""
     if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3 or order.dim() != 1:
         raise ValueError("vertices must be [V,3], faces [T,3] and order [n_faces], got %s, %s, %s"
                          % (tuple(vertices.shape), tuple(faces.shape), tuple(order.shape)))
@@ -882,6 +883,11 @@ def _mesh_sdf_mesh(vertices, faces, order, leaf_size):
     if need < 0:
         raise ValueError("%d faces in leaves of %d make a tree deeper than the walk's 24 levels: use a larger leaf_size"
                          % (order.shape[0], leaf_size))
+    if boxes is not None:
+        _dev(boxes, torch.float32, "boxes")
+        if boxes.numel() * 4 != need:
+            raise ValueError("boxes holds %d bytes, the tree of %d faces in leaves of %d needs %d"
+                             % (boxes.numel() * 4, order.shape[0], leaf_size, need))
     return int(order.shape[0]), need
 
 
@@ -898,14 +904,12 @@ def mesh_bvh_build(vertices, faces, order, leaf_size=4):
 def mesh_sdf_query(points, vertices, faces, order, boxes, leaf_size=4, edge_normals=None, vertex_normals=None, details=True):
     """Nearest face of every point [n,3] f32 -> (sdf [n], closest [n,3], face [n] int32, feature [n] int32); details=False: only sdf, the
     others None (the same bits).  Signed iff edge_normals f32 [T,3,3] and vertex_normals f32 [V,3] are given (both or neither)."""
-    n_faces, need = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
+    n_faces, _ = _mesh_sdf_mesh(vertices, faces, order, leaf_size, boxes)
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("points must be [n,3], got %s" % (tuple(points.shape),))
     if (edge_normals is None) != (vertex_normals is None):
         raise ValueError("edge_normals and vertex_normals go together: both for the signed distance, neither for the unsigned")
-    _dev(points, torch.float32, "points"); _dev(boxes, torch.float32, "boxes")
-    if boxes.numel() * 4 != need:
-        raise ValueError("boxes holds %d bytes, the tree of %d faces in leaves of %d needs %d" % (boxes.numel() * 4, n_faces, leaf_size, need))
+    _dev(points, torch.float32, "points")
     if edge_normals is not None:
         _dev(edge_normals, torch.float32, "edge_normals"); _dev(vertex_normals, torch.float32, "vertex_normals")
         if tuple(edge_normals.shape) != (faces.shape[0], 3, 3) or tuple(vertex_normals.shape) != tuple(vertices.shape):
@@ -931,14 +935,12 @@ def mesh_raycast(rays_o, rays_d, vertices, faces, order, boxes, leaf_size=4, t_m
     on a miss, face [n] int32: -1, bary [n,2]: 0, side [n] int32: +1 front, -1 back, 0 miss); details=False: only t, the others None (the
     same bits).  t in [t_min, t_max], in units of |d|.  any_hit: stop at the first accepted face (occlusion).  cull: None, "back" or
     "front"."""
-    n_faces, need = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
+    n_faces, _ = _mesh_sdf_mesh(vertices, faces, order, leaf_size, boxes)
     if rays_o.dim() != 2 or rays_o.shape[1] != 3 or tuple(rays_d.shape) != tuple(rays_o.shape):
         raise ValueError("rays_o and rays_d must both be [n,3], got %s and %s" % (tuple(rays_o.shape), tuple(rays_d.shape)))
     if cull not in (None, "back", "front"):
         raise ValueError("cull must be None, 'back' or 'front', got %r" % (cull,))
-    _dev(rays_o, torch.float32, "rays_o"); _dev(rays_d, torch.float32, "rays_d"); _dev(boxes, torch.float32, "boxes")
-    if boxes.numel() * 4 != need:
-        raise ValueError("boxes holds %d bytes, the tree of %d faces in leaves of %d needs %d" % (boxes.numel() * 4, n_faces, leaf_size, need))
+    _dev(rays_o, torch.float32, "rays_o"); _dev(rays_d, torch.float32, "rays_d")
     flags = (RAYCAST_ANY_HIT if any_hit else 0) | {None: 0, "back": RAYCAST_CULL_BACK, "front": RAYCAST_CULL_FRONT}[cull]
     n, dev = rays_o.shape[0], rays_o.device
     t = torch.empty(n, device=dev, dtype=torch.float32)
@@ -964,10 +966,7 @@ def _mesh_winding_bytes(n_faces, leaf_size):
 def mesh_winding_build(vertices, faces, order, boxes, leaf_size=4):
     """The per-node moments of csrc/mesh_winding.hip (centroid, radius, area vector, area, second-order tensor) over the tree of
     mesh_bvh_build -> moments f32 [2 P - 1, 20]."""
-    n_faces, need = _mesh_sdf_mesh(vertices, faces, order, leaf_size)
-    _dev(boxes, torch.float32, "boxes")
-    if boxes.numel() * 4 != need:
-        raise ValueError("boxes holds %d bytes, the tree of %d faces in leaves of %d needs %d" % (boxes.numel() * 4, n_faces, leaf_size, need))
+    n_faces, _ = _mesh_sdf_mesh(vertices, faces, order, leaf_size, boxes)
     moments = torch.empty(_mesh_winding_bytes(n_faces, leaf_size) // (4 * MESH_WINDING_ROW), MESH_WINDING_ROW, device=vertices.device,
                           dtype=torch.float32)
     check(_lib().ngp_mesh_winding_build(_ptr(vertices), _ptr(faces), _ptr(order), _ptr(boxes), n_faces, int(leaf_size), _ptr(moments),
