@@ -10,7 +10,9 @@ density = threshold of an Instant-NGP model; the default threshold is the occupa
 0.01 * MAX_SAMPLES / sqrt(3).  The file type follows the suffix of --out (.ply binary little-endian, .obj text).  One JSON line reports
 V, T, the Euler characteristic V - E + T, the number of boundary edges (0 = closed surface) and the times.
 --keep_largest K and --min_component_faces N (both off by default) remove floaters before the file is written (ngp_hip.clean_mesh:
-connected components on the device) and print its report and the topology before and after."""
+connected components on the device) and print its report and the topology before and after.
+--simplify_cell H, --simplify_resolution R or --target_faces N (all off by default, at most one) then make the mesh smaller
+(ngp_hip.simplify_mesh: vertex clustering with quadric representatives, after the cleaning) and print V and T before and after."""
 import argparse
 import json
 import math
@@ -106,6 +108,11 @@ def main(argv=None):
     ap.add_argument("--keep_largest", type=int, default=None, metavar="K",
                     help="clean the mesh before writing it: keep the K connected components of the largest area (ngp_hip.clean_mesh)")
     ap.add_argument("--min_component_faces", type=int, default=0, metavar="N", help="clean the mesh: drop components of fewer than N faces")
+    small = ap.add_mutually_exclusive_group()
+    small.add_argument("--simplify_cell", type=float, default=None, metavar="H",
+                       help="simplify the mesh before writing it: cluster the vertices on a grid of this edge length (ngp_hip.simplify_mesh)")
+    small.add_argument("--simplify_resolution", type=int, default=None, metavar="R", help="simplify: R cells along the longest side of the mesh")
+    small.add_argument("--target_faces", type=int, default=None, metavar="N", help="simplify: the finest grid found that leaves at most N faces")
     ap.add_argument("--scale", type=float, default=0.5)
     # the --sdf fit (fit_sdf_eikonal.py's options); --max_res also sizes the NGP of --ckpt
     ap.add_argument("--steps", type=int, default=500)
@@ -167,6 +174,16 @@ def main(argv=None):
         info.update(clean=dict(report, before=before, seconds=time.time() - t2))
         print("clean_mesh:", json.dumps(info["clean"]))
         print("topology before:", json.dumps(before), "after:", json.dumps(mesh.topology(msh)))
+    if args.simplify_cell is not None or args.simplify_resolution is not None or args.target_faces is not None:      # off by default
+        t_simplify = time.time()
+        before = {"vertices": int(msh.vertices.shape[0]), "faces": int(msh.faces.shape[0])}
+        res = mesh.simplify_mesh(msh, cell=args.simplify_cell, resolution=args.simplify_resolution, target_faces=args.target_faces,
+                                 normals=normals is not None)
+        msh = res.mesh
+        torch.cuda.synchronize()
+        info.update(simplify=dict(vertices=int(msh.vertices.shape[0]), faces=int(msh.faces.shape[0]), before=before, cell=list(res.h),
+                                  grid=list(res.grid), clusters=res.n_clusters, seconds=time.time() - t_simplify))
+        print("simplify_mesh:", json.dumps(info["simplify"]))
     t_write = time.time()
     (mesh.write_ply if args.out.endswith(".ply") else mesh.write_obj)(args.out, msh)
     t3 = time.time()

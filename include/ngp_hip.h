@@ -833,6 +833,54 @@ int ngp_mesh_select_emit(const float* vertices, const float* normals /* may be N
                          const int32_t* vertex_map, const int32_t* face_map, int n_out_vertices, int n_out_faces, float* out_vertices,
                          float* out_normals /* NULL iff normals is */, int32_t* out_faces, void* stream);
 
+/* ---- mesh simplification: vertex clustering on a grid with a quadric-optimal representative per cluster (csrc/mesh_simplify.hip;
+ * DESIGN.md section 3).  vertices f32 [V,3], faces int32 [T,3], 1 <= V, 0 <= T (the package answers V = 0 without a call).
+ * CELLS.  lo[3], inv_h[3], h[3] (f32) and n[3] are HOST arrays the caller chooses: every value finite, inv_h and h positive,
+ * 1 <= n_k <= 2^21 and n_x n_y n_z < 2^63 (every key is then below INT64_MAX).  q_k = floorf((x_k - lo_k) * inv_h_k) in f32 (one subtraction, one multiplication), clamped to [0, n_k - 1] in
+ * float, then key = q_x + n_x (q_y + n_y q_z) as int64.  A vertex with a coordinate that is not finite is BAD: key INT64_MAX, no
+ * cluster, counted.  A face is BAD when an index is outside [0, V) or names a bad vertex: it contributes nothing, face_map -1, counted.
+ * CLUSTERS.  One per distinct key, numbered 0 .. C - 1 by increasing key (a stable sort of the keys, the first slot of every run, a scan).
+ * SURVIVING FACES.  A good face survives when its corners lie in three distinct clusters; survivors keep their input order and corner
+ * order.  Output vertices are the clusters some surviving face names, numbered by increasing key.  Duplicate output faces stay.
+ * QUADRICS, in f64 from the f32 coordinates, relative to the cell centre c = lo + (q + 1/2) h: every good face with nn = (b - a) x
+ * (c' - a) != 0 adds, ONCE to each distinct cluster among its corners, with w = |nn| / 2, n = nn / |nn|, d = -n . (a - c):
+ * A += w n n^T, b += w d n, area vector += nn / 2.  Per cluster also the sum of (v - c) over its vertices and their count.
+ * REPRESENTATIVE.  mean = sum (v - c) / count, mu = regularization tr(A), y = (A + mu I)^-1 (-b + mu mean); y = mean when tr(A) = 0 or
+ * regularization = +inf.  y is clamped to [-h / 2, h / 2] per axis and x = (float)(c + y).  The normal is the normalised area vector, 0
+ * where that is 0.
+ * simplify_bytes : the size of `workspace` for simplify_count (about V + T bytes)
+ * simplify_keys  : keys int64 [V]; zeroes counts int32 [5] = {C, V', T', bad vertices, bad faces} and counts the bad vertices
+ * simplify_count : sorted_keys, order int64 [V] = the keys in ascending order and the stable permutation that sorts them.  Writes
+ *                  vertex_cluster int32 [V] (-1: bad), cluster_out int32 [V] (its first C slots: the output vertex of a cluster or -1),
+ *                  vertex_map int32 [V], face_map int32 [T] (the output vertex / face, -1 for none) and the rest of counts, on the device.
+ *                  T = 0 is allowed (faces and face_map may then be null).  This is all a face count needs: no quadric is formed.
+ * simplify_incidence_keys : keys int64 [3 T]: key 3 f + k is the cluster of corner k of face f, INT64_MAX when the face is bad or has
+ *                  nn = 0, or the cluster repeats that of an earlier corner of the face
+ * simplify_runs_bytes : the size of `runs` (4-byte aligned scratch) for simplify_emit; -1 unless 1 <= V' <= C
+ * simplify_emit  : incidence_keys, incidence_order int64 [3 T] = those keys sorted, stably, and the permutation; 3 T <= 2^31 - 1 (a run's
+ *                  ends are int32).  n_clusters,
+ *                  n_out_vertices, n_out_faces: the host's copies of counts (all >= 1).  Writes out_vertices f32 [V',3], out_normals f32
+ *                  [V',3] (unless NULL) and out_faces int32 [T',3].  A cluster's sums run over its slice of the sorted lists in a fixed
+ *                  order (lane l of a wave takes l, l + 64, ..., then an xor tree): no float atomics, the same input gives the same bytes.
+ * All return -1 without a launch for a null required pointer, a size or grid outside the above, or a regularization that is not > 0. */
+long long ngp_mesh_simplify_bytes(int n_faces, int n_vertices);
+int ngp_mesh_simplify_keys(const float* vertices, int n_vertices, const float* lo /* host [3] */, const float* inv_h /* host [3] */,
+                           const float* h /* host [3] */, const int32_t* n /* host [3] */, int64_t* keys /*[V]*/, int32_t* counts /*[5]*/,
+                           void* stream);
+int ngp_mesh_simplify_count(const int32_t* faces, int n_faces, int n_vertices, const int64_t* sorted_keys, const int64_t* order,
+                            void* workspace, int32_t* vertex_cluster, int32_t* cluster_out, int32_t* vertex_map, int32_t* face_map,
+                            int32_t* counts /*[5]*/, void* stream);
+int ngp_mesh_simplify_incidence_keys(const float* vertices, const int32_t* faces, int n_faces, int n_vertices,
+                                     const int32_t* vertex_cluster, int64_t* keys /*[3 T]*/, void* stream);
+long long ngp_mesh_simplify_runs_bytes(int n_clusters, int n_out_vertices);
+int ngp_mesh_simplify_emit(const float* vertices, const int32_t* faces, int n_faces, int n_vertices, const float* lo /* host [3] */,
+                           const float* inv_h /* host [3] */, const float* h /* host [3] */, const int32_t* n /* host [3] */,
+                           const int64_t* vertex_keys, const int64_t* vertex_order, const int64_t* incidence_keys,
+                           const int64_t* incidence_order, const int32_t* vertex_cluster, const int32_t* cluster_out,
+                           const int32_t* vertex_map, const int32_t* face_map, int n_clusters, int n_out_vertices, int n_out_faces,
+                           double regularization, void* runs, float* out_vertices, float* out_normals /* may be NULL */,
+                           int32_t* out_faces, void* stream);
+
 /* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
  * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
  * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],

@@ -17,8 +17,8 @@
 // unmodified slots), so the number of roots drops by at least one per changed pass: at most V passes in all (the host loop's cap).
 // The skip tests (`changed[r - 1] == 0`, `changed[r] == 0`) read flags of EARLIER launches only.
 //
-//   cc_mark_kernel, cc_root_kernel, cc_scan_*_kernel, cc_assign_*_kernel   used vertices, root flags, the exclusive scan of the flags
-//                       (a wave per CC_CHUNK slots, one block over the chunk totals, the wave walk again) and the labels
+//   cc_mark_kernel, cc_root_kernel, mesh_scan (mesh_scan.h), cc_assign_*_kernel   used vertices, root flags, the exclusive scan of the
+//                       flags (a wave per 512 slots, one block over the chunk totals, the wave walk again) and the labels
 //   cc_edge_keys_kernel, cc_tally_*_kernel, cc_edge_kernel, cc_euler_kernel   the integer columns of the table: integer atomics,
 //                       aggregated in the wave: one atomic per distinct component among its lanes (one component usually owns
 //                       almost everything)
@@ -29,17 +29,17 @@
 //
 // Only integer atomicMin / atomicAdd and flag stores cross workgroups; their results do not depend on arrival order.
 #include "ngp_device.h"
+#include "mesh_scan.h"
 
 namespace ngp {
 
-constexpr int CC_CHUNK = 512;              // slots per wave of the scan: 8 rounds of 64 lanes
 constexpr int CC_BLOCK = 64;               // faces per block of the float sums: one per lane
 constexpr int CC_COLS = 6;                 // int columns of the table: vertices, faces, edges, boundary, non-manifold, euler
 constexpr long long CC_NO_EDGE = 0x7fffffffffffffffll;      // the key of an edge that does not count: sorts behind every real key
 
 struct CcPartial { double area, volume; int32_t lo[3], hi[3]; };         // 40 bytes; lo / hi as ordered keys (cc_key)
 
-__host__ __device__ __forceinline__ long long cc_chunks(long long n) { return (n + CC_CHUNK - 1) / CC_CHUNK; }
+__host__ __device__ __forceinline__ long long cc_chunks(long long n) { return mesh_scan_chunks(n); }
 __host__ __device__ __forceinline__ long long cc_align16(long long b) { return (b + 15) & ~15ll; }
 struct CcWorkspace {
     uint8_t* flags;       // [max(V, T)]: bit 0 used / kept, bit 1 root
@@ -108,63 +108,6 @@ __global__ void __launch_bounds__(256) cc_root_kernel(int n_vertices, const int3
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v >= n_vertices) return;
     if (flags[v] && parent[v] == (int)v) flags[v] = 3;
-}
-
-// ---- the scan of a flag array: index[i] = the number of flagged slots before i where slot i is flagged, else -1 ---------------------
-__global__ void __launch_bounds__(256) cc_scan_count_kernel(const uint8_t* __restrict__ flags, int bit, long long n, int32_t* chunk) {
-    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long long first = wave * CC_CHUNK;
-    if (first >= n) return;
-    const int lane = threadIdx.x & 63;
-    int total = 0;
-    for (int r = 0; r < CC_CHUNK / 64; ++r) {
-        const long long i = first + 64 * r + lane;
-        const bool on = i < n && (flags[i] & bit);
-        total += __popcll(__ballot(on));
-    }
-    if (lane == 0) chunk[wave] = total;
-}
-
-// one block: exclusive scan of the chunk totals in place, their sum (<= n < 2^31) to *total
-__global__ void __launch_bounds__(256) cc_scan_block_kernel(int32_t* __restrict__ chunk, long long chunks, int32_t* __restrict__ total) {
-    __shared__ int part[4];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const long long run = (chunks + 255) / 256;
-    const long long lo = min(t * run, chunks), hi = min(lo + run, chunks);
-    int s = 0;
-    for (long long c = lo; c < hi; ++c) s += chunk[c];
-    const int incl = wave_scan_add_i(s, lane);
-    if (lane == 63) part[wv] = incl;
-    __syncthreads();
-    int base = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k < wv) base += part[k];
-        all += part[k];
-    }
-    if (t == 0) *total = all;
-    int acc = base + incl - s;
-    for (long long c = lo; c < hi; ++c) {
-        const int x = chunk[c];
-        chunk[c] = acc;
-        acc += x;
-    }
-}
-
-__global__ void __launch_bounds__(256) cc_scan_index_kernel(const uint8_t* __restrict__ flags, int bit, long long n,
-                                                            const int32_t* __restrict__ chunk, int32_t* __restrict__ index) {
-    const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const long long first = wave * CC_CHUNK;
-    if (first >= n) return;
-    const int lane = threadIdx.x & 63;
-    int run = chunk[wave];
-    for (int r = 0; r < CC_CHUNK / 64; ++r) {
-        const long long i = first + 64 * r + lane;
-        const bool on = i < n && (flags[i] & bit);
-        const unsigned long long m = __ballot(on);
-        if (i < n) index[i] = on ? run + __popcll(m & ((1ull << lane) - 1ull)) : -1;
-        run += __popcll(m);
-    }
 }
 
 __global__ void __launch_bounds__(256) cc_assign_vertices_kernel(int n_vertices, const int32_t* __restrict__ parent,
@@ -377,12 +320,9 @@ using namespace ngp;
 
 static unsigned cc_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
-// index[i] of the flagged slots of flags[0, n), their number to *total: three launches
+// index[i] of the flagged slots of flags[0, n), their number to *total: three launches (mesh_scan.h)
 static void cc_scan(const CcWorkspace& w, int bit, long long n, int32_t* index, int32_t* total, hipStream_t s) {
-    const long long chunks = cc_chunks(n);
-    hipLaunchKernelGGL(cc_scan_count_kernel, dim3(cc_blocks(chunks, 4)), dim3(256), 0, s, w.flags, bit, n, w.chunk);
-    hipLaunchKernelGGL(cc_scan_block_kernel, dim3(1), dim3(256), 0, s, w.chunk, chunks, total);
-    hipLaunchKernelGGL(cc_scan_index_kernel, dim3(cc_blocks(chunks, 4)), dim3(256), 0, s, w.flags, bit, n, w.chunk, index);
+    mesh_scan(w.flags, bit, n, w.chunk, index, total, s);
 }
 
 extern "C" {

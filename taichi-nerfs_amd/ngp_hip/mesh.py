@@ -10,7 +10,9 @@ boundary, a closed consistently oriented 2-manifold; the exact contract is in DE
 read (the vertex and face counts, to size the outputs).
 
     cc = components(mesh)                              # a label per vertex and face, cc.stats: one row per piece (csrc/mesh_components.hip)
-    mesh, report = clean_mesh(mesh, keep_largest=1)    # drop the floaters"""
+    mesh, report = clean_mesh(mesh, keep_largest=1)    # drop the floaters
+    small = simplify_mesh(mesh, target_faces=50000)    # vertex clustering with quadric representatives (csrc/mesh_simplify.hip)
+    write_ply("scene_small.ply", small.mesh)"""
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -221,6 +223,119 @@ def clean_mesh(mesh, keep_largest=None, min_faces=0, min_area_fraction=0.0, clos
               "area_kept": float(area[keep].sum()), "area_dropped": float(area[~keep].sum()),
               "bad_faces": cc.bad_faces, "unused_vertices": cc.unused_vertices, "kept": np.flatnonzero(keep).tolist()}
     return out, report
+
+
+# ---- a smaller mesh (csrc/mesh_simplify.hip; contract: DESIGN.md section 3, "Simplification") ------------------------------------------
+SIMPLIFY_MAX_RESOLUTION = ops.MESH_SIMPLIFY_MAX_CELLS - 1      # cubic cells: one below the per-axis limit, so every key stays below INT64_MAX
+SIMPLIFY_MAX_PASSES = 32                  # count passes a target_faces search may take
+
+
+class SimplifiedMesh(NamedTuple):
+    mesh: Mesh                              # the output: one vertex per cluster that a surviving face names
+    vertex_map: torch.Tensor                # [V] int32: the output vertex an input vertex became, -1 for a bad vertex or a cluster no face names
+    face_map: torch.Tensor                  # [T] int32: the output face, -1 for a collapsed or bad face
+    lo: tuple                               # the grid: cell q spans lo + [q, q + 1) h, as python floats (f32 values)
+    h: tuple
+    grid: tuple                             # cells per axis
+    n_clusters: int                         # occupied cells
+    bad_faces: int                          # faces with an index outside [0, V) or a bad vertex
+    bad_vertices: int                       # vertices with a coordinate that is not finite
+
+
+def simplify_grid(bounds, cell=None, resolution=None):
+    """Host arithmetic: the clustering grid over bounds = (lo[3], hi[3]) -> (lo, h, n), lo and h float32 [3], n three ints.  cell: the
+    edge length, a scalar or one per axis; resolution: the number of cells along the longest side (cubic cells).  n_k = ceil(extent_k /
+    h_k), at least 1: a vertex on the upper face of the box is clamped into the last cell.  An extent of zero gives one cell."""
+    if (cell is None) == (resolution is None):
+        raise ValueError("give exactly one of cell and resolution")
+    lo, hi = np.asarray(bounds[0], np.float32).reshape(-1), np.asarray(bounds[1], np.float32).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi >= lo).all()):
+        raise ValueError("bounds must be finite lo[3] <= hi[3], got %r" % (bounds,))
+    extent = hi.astype(np.float64) - lo.astype(np.float64)
+    if cell is not None:
+        h = np.broadcast_to(np.asarray(cell, np.float32).reshape(-1), (3,)).copy()
+        if not (np.isfinite(h).all() and (h > 0).all()):
+            raise ValueError("cell must be positive and finite, got %r" % (cell,))
+    else:
+        if int(resolution) != resolution or not 1 <= resolution <= SIMPLIFY_MAX_RESOLUTION:
+            raise ValueError("resolution must be an integer in 1..2^21 - 1, got %r" % (resolution,))
+        longest = float(extent.max())
+        h = np.full(3, longest / int(resolution) if longest > 0 else 1.0, np.float32)
+        if not (h > 0).all():
+            h = np.full(3, 1.0, np.float32)
+    n = np.maximum(np.ceil(extent / h.astype(np.float64)), 1.0)
+    if resolution is not None:
+        n = np.minimum(n, float(resolution))           # h is rounded to float32: the longest side has `resolution` cells, not one more
+    if (n > SIMPLIFY_MAX_RESOLUTION).any():
+        raise ValueError("the grid would have %s cells per axis, 2^21 or more: use a larger cell" % (n.astype(np.int64).tolist(),))
+    return lo, h, tuple(int(x) for x in n)
+
+
+def target_resolution(count, n_target, n_faces, max_resolution=SIMPLIFY_MAX_RESOLUTION, max_passes=SIMPLIFY_MAX_PASSES):
+    """The search of simplify_mesh(target_faces=...), host logic over count(resolution) -> surviving faces.  Resolution 1 leaves no
+    face.  It doubles the resolution until the count passes n_target (the upper bracket: the smallest such power of two), then bisects
+    between that and the power before; every count is one pass, at most max_passes in all.  -> the finest resolution it found with a
+    count <= n_target.  The count is not monotone in the resolution, so this is a good grid, not the best one.  n_target >= n_faces
+    needs no pass: the finest grid."""
+    if int(n_target) != n_target or n_target < 0:
+        raise ValueError("target_faces must be a non-negative integer, got %r" % (n_target,))
+    if n_target >= n_faces:
+        return max_resolution
+    lo, hi, passes, r = 1, None, 0, 2
+    while r <= max_resolution and passes < max_passes:
+        passes += 1
+        if count(r) > n_target:
+            hi = r
+            break
+        lo, r = r, 2 * r
+    while hi is not None and hi - lo > 1 and passes < max_passes:
+        mid = (lo + hi) // 2
+        passes += 1
+        if count(mid) <= n_target:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def simplify_mesh(mesh, cell=None, resolution=None, target_faces=None, bounds=None, regularization=1e-3, normals=True):
+    """A smaller mesh by vertex clustering: the vertices of one grid cell become one vertex, placed where the quadric error of the faces
+    around the cell is least (corners and creases stay; regularization=inf places it at the cell's mean instead), faces with two corners
+    in one cell disappear -> SimplifiedMesh.  mesh: a Mesh or (vertices f32 [V,3], faces int32 [T,3]) on the device; its normals are
+    ignored, normals=True gives the output the normalised area vector of every cluster.  Exactly one of cell (edge length, a scalar or
+    one per axis), resolution (cells along the longest side of bounds) and target_faces (a search over the resolution with the count
+    phase alone, one host read per pass: target_resolution) sets the grid.  bounds = (lo[3], hi[3]): default the box of the finite
+    vertices (one more host read); vertices outside are clamped into the boundary cells.  No vertex moves more than one cell edge per
+    axis.  Duplicate output faces are not removed.  The result is deterministic: the same input gives the same bytes."""
+    if sum(x is not None for x in (cell, resolution, target_faces)) != 1:
+        raise ValueError("give exactly one of cell, resolution and target_faces")
+    vertices, faces = mesh[0], mesh[1]
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    ops._dev(vertices, torch.float32, "vertices")
+    n_faces, n_vertices = ops._mesh_faces(faces, vertices.shape[0])
+    if not float(regularization) > 0.0:
+        raise ValueError("regularization must be positive (inf: the cluster mean), got %r" % (regularization,))
+    dev = vertices.device
+    if bounds is None:
+        finite = torch.isfinite(vertices).all(1, keepdim=True)
+        inf = torch.full((1, 3), float("inf"), device=dev)
+        box = torch.stack([torch.cat([torch.where(finite, vertices, inf), inf]).amin(0),
+                           torch.cat([torch.where(finite, vertices, -inf), -inf]).amax(0)]).tolist()      # a host read: the grid is the host's
+        bounds = box if all(np.isfinite(box[0])) else ([0.0] * 3, [0.0] * 3)
+    if n_vertices == 0:                                # nothing to cluster: every face is bad
+        lo, h, n = simplify_grid(bounds, cell=cell, resolution=1 if target_faces is not None else resolution)
+        empty = Mesh(torch.empty(0, 3, device=dev), torch.empty(0, 3, device=dev, dtype=torch.int32), torch.empty(0, 3, device=dev) if normals else None)
+        return SimplifiedMesh(empty, torch.empty(0, device=dev, dtype=torch.int32), torch.full((n_faces,), -1, device=dev, dtype=torch.int32),
+                              tuple(lo.tolist()), tuple(h.tolist()), n, 0, n_faces, 0)
+    if target_faces is not None:
+        resolution = target_resolution(lambda r: int(ops.mesh_simplify_count(vertices, faces, *simplify_grid(bounds, resolution=r)).counts[2]),
+                                       target_faces, n_faces)
+    lo, h, n = simplify_grid(bounds, cell=cell, resolution=resolution)
+    st = ops.mesh_simplify_count(vertices, faces, lo, h, n)
+    n_clusters, n_v, n_f, bad_vertices, bad_faces = st.counts.tolist()                # the one synchronisation between the phases
+    v, nrm, f = ops.mesh_simplify_emit(vertices, faces, st, n_clusters, n_v, n_f, regularization=regularization, normals=bool(normals))
+    return SimplifiedMesh(Mesh(v, f, nrm), st.vertex_map, st.face_map, tuple(lo.tolist()), tuple(h.tolist()), n, n_clusters, bad_faces, bad_vertices)
 
 
 # ---- files (host code) -------------------------------------------------------------------------------------------------------------

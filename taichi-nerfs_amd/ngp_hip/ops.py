@@ -1139,6 +1139,84 @@ def mesh_select(vertices, normals, faces, vertex_component, face_component, keep
     return out_v, out_n, out_f, vertex_map, face_map
 
 
+# ---------------------------------------------------------------------------------------------------- mesh simplification
+MESH_SIMPLIFY_MAX_CELLS = 2**21       # per axis: the cell key fits 63 bits; 2^21 on all three axes is refused (its last key is INT64_MAX)
+MESH_SIMPLIFY_COUNTS = ("clusters", "vertices", "faces", "bad_vertices", "bad_faces")
+
+
+def _mesh_simplify_grid(lo, h, n):
+    """-> the four host arrays of the C ABI (lo, inv_h = 1 / h in f32, h, n); the contract's conditions are checked here."""
+    lo, h = np.asarray(lo, np.float32).reshape(-1), np.asarray(h, np.float32).reshape(-1)
+    n = [int(x) for x in n]
+    if lo.shape != (3,) or h.shape != (3,) or len(n) != 3:
+        raise ValueError("lo, h and n must hold three values each")
+    inv_h = np.float32(1.0) / h if (h > 0).all() else np.zeros(3, np.float32)
+    if not (np.isfinite(lo).all() and np.isfinite(h).all() and (h > 0).all() and np.isfinite(inv_h).all() and (inv_h > 0).all()):
+        raise ValueError("lo must be finite and h positive and finite with a finite positive 1 / h in float32, got lo=%r h=%r" % (lo.tolist(), h.tolist()))
+    if not all(1 <= x <= MESH_SIMPLIFY_MAX_CELLS for x in n) or n[0] * n[1] * n[2] >= 2**63:
+        raise ValueError("every n must be in 1..2^21 (cells per axis) and their product below 2^63, got %r" % (n,))
+    return (ctypes.c_float * 3)(*lo.tolist()), (ctypes.c_float * 3)(*inv_h.tolist()), (ctypes.c_float * 3)(*h.tolist()), (ctypes.c_int32 * 3)(*n)
+
+
+def mesh_simplify_count(vertices, faces, lo, h, n):
+    """The count phase of the simplification (csrc/mesh_simplify.hip) on the grid lo + [0, n) h: cell keys, their stable torch.sort,
+    the cluster numbering, surviving faces and the two maps -> a SimpleNamespace with vertex_map int32 [V], face_map int32 [T], counts
+    int32 [5] (MESH_SIMPLIFY_COUNTS) ON THE DEVICE, and what mesh_simplify_emit needs.  No quadric is formed, nothing is read back.
+    V >= 1; T = 0 is allowed."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    _dev(vertices, torch.float32, "vertices")
+    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
+    if n_vertices < 1:
+        raise ValueError("mesh_simplify_count needs at least one vertex")
+    grid = _mesh_simplify_grid(lo, h, n)
+    dev = vertices.device
+    keys = torch.empty(n_vertices, device=dev, dtype=torch.int64)
+    counts = torch.empty(5, device=dev, dtype=torch.int32)
+    check(_lib().ngp_mesh_simplify_keys(_ptr(vertices), n_vertices, *grid, _ptr(keys), _ptr(counts), _stream()), "ngp_mesh_simplify_keys")
+    keys, order = torch.sort(keys, stable=True)
+    workspace = torch.empty(_lib().ngp_mesh_simplify_bytes(n_faces, n_vertices), device=dev, dtype=torch.uint8)
+    st = SimpleNamespace(grid=grid, vertex_keys=keys, vertex_order=order, counts=counts,
+                         vertex_cluster=torch.empty(n_vertices, device=dev, dtype=torch.int32),
+                         cluster_out=torch.empty(n_vertices, device=dev, dtype=torch.int32),
+                         vertex_map=torch.empty(n_vertices, device=dev, dtype=torch.int32),
+                         face_map=torch.empty(n_faces, device=dev, dtype=torch.int32))
+    check(_lib().ngp_mesh_simplify_count(_ptr(faces), n_faces, n_vertices, _ptr(keys), _ptr(order), _ptr(workspace), _ptr(st.vertex_cluster),
+                                         _ptr(st.cluster_out), _ptr(st.vertex_map), _ptr(st.face_map), _ptr(counts), _stream()),
+          "ngp_mesh_simplify_count")
+    return st
+
+
+def mesh_simplify_emit(vertices, faces, state, n_clusters, n_out_vertices, n_out_faces, regularization=1e-3, normals=True):
+    """The second phase, after mesh_simplify_count on the same mesh (state) and with the host's copies of its counts: incidence keys,
+    their stable torch.sort, the per-cluster sums and solves, the surviving faces -> (vertices f32 [V',3], normals f32 [V',3] or None,
+    faces int32 [T',3]).  Nothing survives: empty tensors, no launch."""
+    regularization = float(regularization)
+    if not regularization > 0.0:
+        raise ValueError("regularization must be positive (inf: the cluster mean), got %r" % (regularization,))
+    _dev(vertices, torch.float32, "vertices")
+    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
+    dev = vertices.device
+    out_v = torch.empty(n_out_vertices, 3, device=dev, dtype=torch.float32)
+    out_n = torch.empty(n_out_vertices, 3, device=dev, dtype=torch.float32) if normals else None
+    out_f = torch.empty(n_out_faces, 3, device=dev, dtype=torch.int32)
+    if n_out_vertices == 0 or n_out_faces == 0:
+        return out_v, out_n, out_f
+    if 3 * n_faces >= 2**31:
+        raise ValueError("the mesh has %d faces; the simplification's incidence list holds at most 2^31 - 1 corners: simplify it in parts" % n_faces)
+    keys = torch.empty(3 * n_faces, device=dev, dtype=torch.int64)
+    check(_lib().ngp_mesh_simplify_incidence_keys(_ptr(vertices), _ptr(faces), n_faces, n_vertices, _ptr(state.vertex_cluster), _ptr(keys),
+                                                  _stream()), "ngp_mesh_simplify_incidence_keys")
+    keys, order = torch.sort(keys, stable=True)
+    runs = torch.empty(_lib().ngp_mesh_simplify_runs_bytes(n_clusters, n_out_vertices) // 4, device=dev, dtype=torch.int32)
+    check(_lib().ngp_mesh_simplify_emit(_ptr(vertices), _ptr(faces), n_faces, n_vertices, *state.grid, _ptr(state.vertex_keys),
+                                        _ptr(state.vertex_order), _ptr(keys), _ptr(order), _ptr(state.vertex_cluster),
+                                        _ptr(state.cluster_out), _ptr(state.vertex_map), _ptr(state.face_map), int(n_clusters),
+                                        int(n_out_vertices), int(n_out_faces), regularization, _ptr(runs), _ptr(out_v), _ptr(out_n),
+                                        _ptr(out_f), _stream()), "ngp_mesh_simplify_emit")
+    return out_v, out_n, out_f
+
+
 # ---------------------------------------------------------------------------------------------------- surface rendering
 def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
     _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
