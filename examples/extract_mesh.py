@@ -12,7 +12,13 @@ V, T, the Euler characteristic V - E + T, the number of boundary edges (0 = clos
 --keep_largest K and --min_component_faces N (both off by default) remove floaters before the file is written (ngp_hip.clean_mesh:
 connected components on the device) and print its report and the topology before and after.
 --simplify_cell H, --simplify_resolution R or --target_faces N (all off by default, at most one) then make the mesh smaller
-(ngp_hip.simplify_mesh: vertex clustering with quadric representatives, after the cleaning) and print V and T before and after."""
+(ngp_hip.simplify_mesh: vertex clustering with quadric representatives, after the cleaning) and print V and T before and after.
+--smooth N (off by default) runs N iterations of Taubin smoothing after the cleaning and before the simplification
+(ngp_hip.smooth_mesh with boundary="fixed": the staircase of the grid goes, the faces stay as they are); no coordinate moves farther than
+--smooth_max_move CELLS (default 0.5) spacings of the extraction grid.  It prints one JSON line: the seconds, the boundary vertices, the
+mean and the largest displacement in cells; with --sdf, where the true surface is known, also the mean distance of the vertices from
+the sphere (in cells) and the mean angle between the face normals and the sphere's (in degrees), before and after.  The normals of a
+smoothed mesh are ngp_hip.vertex_normals of the new positions."""
 import argparse
 import json
 import math
@@ -93,6 +99,19 @@ def train_procedural_model(steps, dev, wh=100, n_views=40, batch=8192):
     return model, thr
 
 
+def sphere_errors(msh, cell):
+    """(mean | |v - 0.5| - 0.3 | over the vertices in cells, mean angle in degrees between the face normals and the sphere's normal at the
+    face centroids) of a mesh of the --sdf sphere."""
+    v, f = msh.vertices.double(), msh.faces.long()
+    if not f.shape[0]:
+        return None, None
+    dist = ((v - 0.5).norm(dim=1) - 0.3).abs().mean() / cell
+    a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    n = F.normalize(torch.cross(b - a, c - a, dim=1), dim=1)
+    cos = (n * F.normalize((a + b + c) / 3 - 0.5, dim=1)).sum(1).clamp(-1.0, 1.0)
+    return float(dist), float(torch.rad2deg(torch.acos(cos)).mean())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     mode = ap.add_mutually_exclusive_group(required=True)
@@ -113,6 +132,10 @@ def main(argv=None):
                        help="simplify the mesh before writing it: cluster the vertices on a grid of this edge length (ngp_hip.simplify_mesh)")
     small.add_argument("--simplify_resolution", type=int, default=None, metavar="R", help="simplify: R cells along the longest side of the mesh")
     small.add_argument("--target_faces", type=int, default=None, metavar="N", help="simplify: the finest grid found that leaves at most N faces")
+    ap.add_argument("--smooth", type=int, default=0, metavar="N",
+                    help="smooth the mesh before writing it: N Taubin iterations with the boundary fixed (ngp_hip.smooth_mesh); 0: off")
+    ap.add_argument("--smooth_max_move", type=float, default=0.5, metavar="CELLS",
+                    help="smoothing moves no coordinate farther than this many spacings of the extraction grid")
     ap.add_argument("--scale", type=float, default=0.5)
     # the --sdf fit (fit_sdf_eikonal.py's options); --max_res also sizes the NGP of --ckpt
     ap.add_argument("--steps", type=int, default=500)
@@ -145,6 +168,7 @@ def main(argv=None):
         t1 = time.time()
         msh, grid = mesh.extract_mesh(fn, args.resolution, 0.0 if args.threshold is None else args.threshold,
                                       bounds=((0.0, 0.0, 0.0), (1.0, 1.0, 1.0)), normals=normals, sign=-1, return_grid=True)
+        cell = [1.0 / args.resolution] * 3
     else:
         from modules.networks import NGP
         from modules.rendering import MAX_SAMPLES
@@ -164,6 +188,7 @@ def main(argv=None):
         with torch.autocast("cuda", dtype=torch.float16):                  # the evaluation loops' numerics: density runs the fused kernels
             msh, grid = mesh.extract_mesh(model, args.resolution, thr, normals=normals, return_grid=True)
         info.update(threshold=thr)
+        cell = mesh.grid_spacing(model.xyz_min.reshape(3).tolist(), model.xyz_max.reshape(3).tolist(), args.resolution)[1]
     torch.cuda.synchronize()
     t2 = time.time()
     if args.keep_largest is not None or args.min_component_faces > 0:        # off by default: the output is then what it always was
@@ -174,6 +199,28 @@ def main(argv=None):
         info.update(clean=dict(report, before=before, seconds=time.time() - t2))
         print("clean_mesh:", json.dumps(info["clean"]))
         print("topology before:", json.dumps(before), "after:", json.dumps(mesh.topology(msh)))
+    if args.smooth > 0:                                                      # off by default
+        if not args.smooth_max_move >= 0.0:
+            raise SystemExit("--smooth_max_move must be >= 0")
+        torch.cuda.synchronize()
+        t_smooth = time.time()
+        res = mesh.smooth_mesh(msh, iterations=args.smooth, boundary="fixed", max_move=[args.smooth_max_move * c for c in cell],
+                               normals=normals is not None)
+        torch.cuda.synchronize()
+        seconds = time.time() - t_smooth
+        moved = (res.mesh.vertices - msh.vertices).abs() / torch.tensor(cell, device=dev, dtype=torch.float32)
+        found = moved.numel() > 0
+        report = dict(iterations=args.smooth, seconds=seconds, boundary_vertices=res.adjacency.boundary_vertices,
+                      bad_faces=res.bad_faces, bad_vertices=res.bad_vertices, max_move_cells=args.smooth_max_move,
+                      mean_displacement_cells=float(moved.norm(dim=1).mean()) if found else None,
+                      max_displacement_cells=float(moved.max()) if found else None)
+        if args.sdf:
+            d0, a0 = sphere_errors(msh, cell[0])
+            d1, a1 = sphere_errors(res.mesh, cell[0])
+            report.update(sphere_distance_cells={"before": d0, "after": d1}, face_normal_error_degrees={"before": a0, "after": a1})
+        msh = res.mesh
+        info.update(smooth=report)
+        print("smooth_mesh:", json.dumps(report))
     if args.simplify_cell is not None or args.simplify_resolution is not None or args.target_faces is not None:      # off by default
         t_simplify = time.time()
         before = {"vertices": int(msh.vertices.shape[0]), "faces": int(msh.faces.shape[0])}

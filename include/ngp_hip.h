@@ -881,6 +881,61 @@ int ngp_mesh_simplify_emit(const float* vertices, const int32_t* faces, int n_fa
                            double regularization, void* runs, float* out_vertices, float* out_normals /* may be NULL */,
                            int32_t* out_faces, void* stream);
 
+/* ---- mesh smoothing: a vertex adjacency built on the device, Taubin's lambda | mu passes over it with a bounded displacement, and
+ * area-weighted vertex normals (csrc/mesh_smooth.hip; DESIGN.md section 3, "Smoothing").  vertices f32 [V,3], faces int32 [T,3],
+ * 1 <= V, 1 <= T, 6 T <= 2^31 - 1 (the package answers V = 0 and T = 0 without a call).
+ * BAD FACES.  A face with an index outside [0, V), or with a repeated index, is BAD: it contributes nothing and is counted.
+ * BAD VERTICES.  A vertex with a coordinate that is not finite is BAD: it never moves and keeps its bits, its neighbours leave it out of
+ * their sums (their degree drops), it is counted.  A face that names a bad vertex is still a good face: the adjacency is integer
+ * arithmetic only and depends on the set of faces alone, not on their order, their corner rotation or the schedule.
+ * ADJACENCY (CSR).  Every good face emits six directed keys u V + w (int64), both directions of its three edges; a bad face emits six
+ * times INT64_MAX.  sorted_keys = those keys in ascending order.  One run of equal keys is one directed edge: E2 runs in all.
+ * row_start int32 [V + 1], neighbours int32 [6 T] (its first E2 slots are written), multiplicity uint8 [6 T] (likewise): the neighbours
+ * of vertex v are neighbours[row_start[v] .. row_start[v + 1]), distinct and ascending; multiplicity is the run's length, the number of
+ * good faces that use the undirected edge in either orientation, saturated at 255.  vertex_flags uint8 [V]: bit 0 BOUNDARY (some
+ * incident edge has multiplicity 1), bit 1 NON-MANIFOLD (some incident edge has multiplicity >= 3), bit 2 UNUSED (no good face names the
+ * vertex), bit 3 BAD.  counts int32 [4] = {E2, bad faces, bad vertices, boundary vertices}, on the device.
+ * adjacency_bytes : the size of `workspace` for adjacency_build (about 30 T bytes); -1 for a T outside the limits
+ * adjacency_keys  : keys int64 [6 T]; zeroes counts and counts the bad faces
+ * adjacency_build : writes row_start, neighbours, multiplicity, vertex_flags and the rest of counts.  Nothing is read back: neighbours
+ *                   and multiplicity are allocated at their bound 6 T, and a smoothing pass needs no more than row_start.
+ * ONE SMOOTHING PASS (a lane per vertex) reads x_in and writes x_out, which must not be the same array.  N(i) = the row of i without
+ * its bad neighbours; with boundary_mode CURVE a boundary vertex keeps only the neighbours across edges of multiplicity 1, so a boundary
+ * smooths along itself.  x_out_i = x_in_i, bit for bit, when i is bad or unused, when fixed[i] != 0 (fixed uint8 [V], may be NULL), when
+ * N(i) is empty, or when boundary_mode is FIXED and i is a boundary vertex; FREE treats every vertex alike.  Otherwise, per coordinate
+ * and in f64 from the f32 values, every operation rounded once (no contraction):
+ *     s = sum over j in N(i) of x_j, serially in ascending j;  m = s / |N(i)|;  y = x_i + factor (m - x_i);  x' = (float)y;
+ *     then in f32: lo = x0_i - max_move, hi = x0_i + max_move;  x' < lo ? lo : x';  x' > hi ? hi : x'.
+ * max_move: a HOST array of three f32, each >= 0, +inf = no bound on that axis (all three +inf: x0 is not read and may be NULL).  The
+ * clamp makes |x' - x0| <= max_move hold up to the one rounding of x0 -+ max_move, after any number of passes.
+ * mesh_smooth     : n_iterations Taubin iterations: a pass with factor lambda, then one with factor mu; mu == 0 is the plain Laplacian,
+ *                   lambda passes only.  The positions start in x_a; pass p reads x_a and writes x_b for even p, the reverse for odd p,
+ *                   so the result is in x_a after an even number of passes (n_iterations (mu == 0 ? 1 : 2)) and in x_b after an odd one.
+ *                   x0 f32 [V,3]: the original positions, neither x_a nor x_b.  n_slots: the allocated length of neighbours and
+ *                   multiplicity (rows are cut there); no index read from the CSR is followed outside [0, V).
+ * vertex_normals_keys : keys int64 [3 T]: key 3 f + k is corner k of face f, INT64_MAX for a bad face
+ * vertex_normals  : sorted_keys, order int64 [3 T] = those keys sorted, stably, and the permutation.  normals f32 [V,3]: the f64 sum of
+ *                   the area vectors (b - a) x (c - a) / 2 of the vertex's faces in ascending slot order, divided by its length and
+ *                   rounded to f32; 0 where the sum is 0 or not finite.  No float atomics: the same input gives the same bytes.
+ * All return -1 without a launch for a null required pointer, a size outside the limits, a lambda or mu that is not finite, a max_move
+ * that is negative or NaN, an unknown boundary_mode, or x_a == x_b. */
+#define NGP_MESH_SMOOTH_FIXED 0
+#define NGP_MESH_SMOOTH_CURVE 1
+#define NGP_MESH_SMOOTH_FREE 2
+long long ngp_mesh_adjacency_bytes(int n_faces);
+int ngp_mesh_adjacency_keys(const int32_t* faces, int n_faces, int n_vertices, int64_t* keys /*[6 T]*/, int32_t* counts /*[4]*/,
+                            void* stream);
+int ngp_mesh_adjacency_build(const float* vertices, int n_faces, int n_vertices, const int64_t* sorted_keys, void* workspace,
+                             int32_t* row_start /*[V + 1]*/, int32_t* neighbours /*[6 T]*/, uint8_t* multiplicity /*[6 T]*/,
+                             uint8_t* vertex_flags /*[V]*/, int32_t* counts /*[4]*/, void* stream);
+int ngp_mesh_smooth(float* x_a, float* x_b, const float* x0 /* may be NULL without a bound */, const int32_t* row_start,
+                    const int32_t* neighbours, const uint8_t* multiplicity, const uint8_t* vertex_flags,
+                    const uint8_t* fixed /* may be NULL */, int n_vertices, long long n_slots, int n_iterations, double lambda, double mu,
+                    int boundary_mode, const float* max_move /* host [3] */, void* stream);
+int ngp_mesh_vertex_normals_keys(const int32_t* faces, int n_faces, int n_vertices, int64_t* keys /*[3 T]*/, void* stream);
+int ngp_mesh_vertex_normals(const float* vertices, const int32_t* faces, int n_faces, int n_vertices, const int64_t* sorted_keys,
+                            const int64_t* order, float* normals /*[V,3]*/, void* stream);
+
 /* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
  * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
  * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],

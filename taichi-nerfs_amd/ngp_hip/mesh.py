@@ -12,7 +12,9 @@ read (the vertex and face counts, to size the outputs).
     cc = components(mesh)                              # a label per vertex and face, cc.stats: one row per piece (csrc/mesh_components.hip)
     mesh, report = clean_mesh(mesh, keep_largest=1)    # drop the floaters
     small = simplify_mesh(mesh, target_faces=50000)    # vertex clustering with quadric representatives (csrc/mesh_simplify.hip)
-    write_ply("scene_small.ply", small.mesh)"""
+    write_ply("scene_small.ply", small.mesh)
+    smooth = smooth_mesh(mesh, iterations=10, max_move=0.5 * h)     # Taubin smoothing over a device-built adjacency (csrc/mesh_smooth.hip)
+    n = vertex_normals(smooth.mesh)                    # area-weighted, deterministic"""
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -336,6 +338,101 @@ def simplify_mesh(mesh, cell=None, resolution=None, target_faces=None, bounds=No
     n_clusters, n_v, n_f, bad_vertices, bad_faces = st.counts.tolist()                # the one synchronisation between the phases
     v, nrm, f = ops.mesh_simplify_emit(vertices, faces, st, n_clusters, n_v, n_f, regularization=regularization, normals=bool(normals))
     return SimplifiedMesh(Mesh(v, f, nrm), st.vertex_map, st.face_map, tuple(lo.tolist()), tuple(h.tolist()), n, n_clusters, bad_faces, bad_vertices)
+
+
+# ---- smoothing (csrc/mesh_smooth.hip; contract: DESIGN.md section 3, "Smoothing") -------------------------------------------------------
+SMOOTH_PASS_BAND = 0.1                    # Taubin's k_pb behind mu=None
+
+
+class MeshAdjacency(NamedTuple):
+    """The vertex adjacency as CSR, on the device: the neighbours of vertex v are neighbours[row_start[v] : row_start[v + 1]], distinct
+    and ascending.  Built from the good faces (indices inside [0, V), no repeated index) alone."""
+    row_start: torch.Tensor                 # [V + 1] int32
+    neighbours: torch.Tensor                # [E2] int32: E2 directed edges, two per undirected edge
+    multiplicity: torch.Tensor              # [E2] uint8: the good faces that use the edge, in either orientation; saturates at 255
+    vertex_flags: torch.Tensor              # [V] uint8: bit 0 boundary, bit 1 non-manifold, bit 2 unused, bit 3 bad (not finite)
+    bad_faces: int
+    bad_vertices: int
+    boundary_vertices: int
+
+    @property
+    def degree(self):
+        """[V] int32: the number of distinct neighbours (bad ones included)."""
+        return self.row_start[1:] - self.row_start[:-1]
+
+    @property
+    def boundary(self):
+        """[V] bool: some incident edge is used by exactly one face."""
+        return (self.vertex_flags & ops.MESH_FLAG_BOUNDARY) != 0
+
+
+class SmoothedMesh(NamedTuple):
+    mesh: Mesh                              # the input's faces tensor, new vertices, normals recomputed (or None)
+    adjacency: MeshAdjacency
+    bad_faces: int
+    bad_vertices: int
+
+
+def _trim_adjacency(raw):
+    row_start, neighbours, multiplicity, flags, counts = raw
+    edges, bad_faces, bad_vertices, boundary_vertices = counts.tolist()          # the one host read
+    return MeshAdjacency(row_start, neighbours[:edges], multiplicity[:edges], flags, bad_faces, bad_vertices, boundary_vertices)
+
+
+def adjacency(mesh):
+    """The vertex adjacency of a Mesh or a (vertices, faces) pair of device tensors -> MeshAdjacency.  One host read (the number of
+    directed edges, to trim the arrays, with the three counters).  It depends on the set of good faces alone: not on their order, not on
+    the rotation of their corners."""
+    return _trim_adjacency(ops.mesh_adjacency(mesh[0], mesh[1]))
+
+
+def vertex_normals(mesh_or_vertices, faces=None):
+    """Area-weighted vertex normals f32 [V,3] of a Mesh, a (vertices, faces) pair, or vertices with faces=...: the sum of the area
+    vectors (b - a) x (c - a) / 2 of the vertex's good faces, in f64 and in a fixed order, normalised; 0 where that sum is 0 or not
+    finite (an unused vertex, area vectors that cancel, a face with a vertex that is not finite).  The weighting is by area, not by
+    angle as mesh_sdf.pseudonormals: the two agree on a flat neighbourhood and differ elsewhere.  No host read."""
+    vertices = mesh_or_vertices if faces is not None else mesh_or_vertices[0]
+    faces = faces if faces is not None else mesh_or_vertices[1]
+    return ops.mesh_vertex_normals(vertices, faces)
+
+
+def taubin_mu(lam, pass_band=SMOOTH_PASS_BAND):
+    """Taubin's second factor for the pass band k_pb: mu = 1 / (k_pb - 1 / lam), negative and a little larger than lam in magnitude."""
+    lam, pass_band = float(lam), float(pass_band)
+    if not lam > 0.0 or not 0.0 < pass_band < 1.0 / lam:
+        raise ValueError("pass_band must lie in (0, 1 / lam) for a positive lam, got lam=%r pass_band=%r" % (lam, pass_band))
+    return 1.0 / (pass_band - 1.0 / lam)
+
+
+def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, pass_band=None, boundary="fixed", fixed=None, max_move=None, normals=True,
+                adjacency=None):
+    """Taubin's lambda | mu smoothing -> SmoothedMesh.  One iteration moves every vertex towards the mean of its neighbours by the factor
+    lam, then by the factor mu (negative: it undoes the shrinkage of the first pass).  mu=None, or a pass_band, sets mu = taubin_mu(lam,
+    pass_band or 0.1); mu=0.0 is the plain Laplacian, lam passes only.  boundary: "fixed" -- boundary vertices stay; "curve" -- they smooth
+    along the boundary only; "free" -- they are vertices like the others (an open mesh then shrinks inwards).  fixed: bool / uint8 [V] on
+    the device, vertices that stay (their neighbours still see them).  max_move: a scalar or three values in world units, the bound on
+    every coordinate's displacement from the INPUT position, for any number of iterations (None: no bound).  normals: True -- the result
+    carries vertex_normals of the new positions, whether or not the input had normals; False -- it carries none.  The result's mesh
+    shares the input's faces tensor.  iterations=0 returns the input positions bit for bit.  Vertices that are not finite stay as they
+    are and are left out of their neighbours' means; faces with an index outside [0, V) or a repeated index are ignored; both are counted.
+    adjacency: the MeshAdjacency of this mesh's faces if it is at hand; then nothing is read back from the device, otherwise one read
+    after the last launch (the counters of the adjacency built here).  Deterministic: the same input gives the same bytes."""
+    vertices, faces = mesh[0], mesh[1]
+    if mu is None or pass_band is not None:
+        mu = taubin_mu(lam, SMOOTH_PASS_BAND if pass_band is None else pass_band)
+    raw = None
+    if adjacency is None:
+        raw = ops.mesh_adjacency(vertices, faces)
+        row_start, neighbours, multiplicity, flags = raw[:4]
+    else:
+        row_start, neighbours, multiplicity, flags = adjacency[:4]
+    if max_move is not None:
+        max_move = np.broadcast_to(np.asarray(max_move, np.float64).reshape(-1), (3,))
+    x = ops.mesh_smooth(vertices, row_start, neighbours, multiplicity, flags, iterations, lam, mu, boundary, fixed, max_move)
+    nrm = ops.mesh_vertex_normals(x, faces) if normals else None
+    if raw is not None:
+        adjacency = _trim_adjacency(raw)
+    return SmoothedMesh(Mesh(x, faces, nrm), adjacency, adjacency.bad_faces, adjacency.bad_vertices)
 
 
 # ---- files (host code) -------------------------------------------------------------------------------------------------------------

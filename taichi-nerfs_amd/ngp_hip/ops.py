@@ -1217,6 +1217,105 @@ def mesh_simplify_emit(vertices, faces, state, n_clusters, n_out_vertices, n_out
     return out_v, out_n, out_f
 
 
+# ---------------------------------------------------------------------------------------------------- mesh smoothing
+MESH_ADJACENCY_COUNTS = ("edges", "bad_faces", "bad_vertices", "boundary_vertices")
+MESH_SMOOTH_MODES = {"fixed": _lib_mod._ABI.defines["NGP_MESH_SMOOTH_FIXED"], "curve": _lib_mod._ABI.defines["NGP_MESH_SMOOTH_CURVE"],
+                     "free": _lib_mod._ABI.defines["NGP_MESH_SMOOTH_FREE"]}
+MESH_FLAG_BOUNDARY, MESH_FLAG_NONMANIFOLD, MESH_FLAG_UNUSED, MESH_FLAG_BAD = 1, 2, 4, 8
+
+
+def _mesh_smooth_sizes(vertices, faces):
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    _dev(vertices, torch.float32, "vertices")
+    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
+    if 6 * n_faces >= 2**31:
+        raise ValueError("the mesh has %d faces; the adjacency's key list holds at most 2^31 - 1 directed edges" % n_faces)
+    return n_faces, n_vertices
+
+
+def mesh_adjacency(vertices, faces):
+    """The vertex adjacency of a mesh as CSR, built on the device (csrc/mesh_smooth.hip): six directed keys per face, their torch.sort,
+    runs, rows -> (row_start int32 [V + 1], neighbours int32 [6 T], multiplicity uint8 [6 T], vertex_flags uint8 [V], counts int32 [4]
+    (MESH_ADJACENCY_COUNTS) ON THE DEVICE).  Only the first counts[0] slots of neighbours and multiplicity are written; nothing is read
+    back.  V = 0 or T = 0: no launch (every face bad, every vertex unused)."""
+    n_faces, n_vertices = _mesh_smooth_sizes(vertices, faces)
+    dev = vertices.device
+    row_start = torch.zeros(n_vertices + 1, device=dev, dtype=torch.int32)
+    neighbours = torch.empty(6 * n_faces, device=dev, dtype=torch.int32)
+    multiplicity = torch.empty(6 * n_faces, device=dev, dtype=torch.uint8)
+    if n_faces == 0 or n_vertices == 0:
+        bad = ~torch.isfinite(vertices).all(1)
+        flags = MESH_FLAG_UNUSED + MESH_FLAG_BAD * bad.to(torch.uint8)
+        counts = torch.tensor([0, n_faces, 0, 0], device=dev, dtype=torch.int32)
+        counts[2] = bad.sum()
+        return row_start, neighbours, multiplicity, flags, counts
+    keys = torch.empty(6 * n_faces, device=dev, dtype=torch.int64)
+    counts = torch.empty(4, device=dev, dtype=torch.int32)
+    check(_lib().ngp_mesh_adjacency_keys(_ptr(faces), n_faces, n_vertices, _ptr(keys), _ptr(counts), _stream()), "ngp_mesh_adjacency_keys")
+    keys = torch.sort(keys).values
+    workspace = torch.empty(_lib().ngp_mesh_adjacency_bytes(n_faces), device=dev, dtype=torch.uint8)
+    flags = torch.empty(n_vertices, device=dev, dtype=torch.uint8)
+    check(_lib().ngp_mesh_adjacency_build(_ptr(vertices), n_faces, n_vertices, _ptr(keys), _ptr(workspace), _ptr(row_start), _ptr(neighbours),
+                                          _ptr(multiplicity), _ptr(flags), _ptr(counts), _stream()), "ngp_mesh_adjacency_build")
+    return row_start, neighbours, multiplicity, flags, counts
+
+
+def mesh_smooth(vertices, row_start, neighbours, multiplicity, vertex_flags, iterations, lam, mu, boundary="fixed", fixed=None,
+                max_move=None):
+    """`iterations` Taubin iterations (a lambda pass, then a mu pass; mu = 0: lambda passes only) over the CSR of mesh_adjacency ->
+    new positions f32 [V,3]; `vertices` is not written.  max_move: None or three floats >= 0 (inf: no bound on that axis), the bound
+    on the displacement from `vertices`.  fixed: uint8 / bool [V] on the device or None.  No host read."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    _dev(vertices, torch.float32, "vertices")
+    n_vertices = int(vertices.shape[0])
+    _dev(row_start, torch.int32, "row_start"); _dev(neighbours, torch.int32, "neighbours")
+    _dev(multiplicity, torch.uint8, "multiplicity"); _dev(vertex_flags, torch.uint8, "vertex_flags")
+    if tuple(row_start.shape) != (n_vertices + 1,) or tuple(vertex_flags.shape) != (n_vertices,) or neighbours.dim() != 1 \
+            or multiplicity.shape != neighbours.shape:
+        raise ValueError("row_start must be [V + 1], vertex_flags [V], neighbours and multiplicity [E] alike")
+    if boundary not in MESH_SMOOTH_MODES:
+        raise ValueError('boundary must be "fixed", "curve" or "free", got %r' % (boundary,))
+    iterations, lam, mu = int(iterations), float(lam), float(mu)
+    if iterations < 0 or not (np.isfinite(lam) and np.isfinite(mu)):
+        raise ValueError("iterations must be >= 0 and lam, mu finite, got %r, %r, %r" % (iterations, lam, mu))
+    move = np.full(3, np.inf, np.float32) if max_move is None else np.broadcast_to(np.asarray(max_move, np.float32).reshape(-1), (3,))
+    if not (move >= 0).all():
+        raise ValueError("max_move must be >= 0 (inf: no bound), got %r" % (max_move,))
+    if fixed is not None:
+        if not fixed.is_cuda:
+            raise RuntimeError("fixed must live on the GPU: libngp_hip has no CPU path (got device %s)" % fixed.device)
+        if tuple(fixed.shape) != (n_vertices,):
+            raise ValueError("fixed must be [V]")
+        fixed = fixed.to(torch.uint8).contiguous()
+    x_a = vertices.clone()
+    passes = iterations * (1 if mu == 0.0 else 2)
+    if n_vertices == 0 or passes == 0 or neighbours.shape[0] == 0:          # no edge: every vertex is unused, nothing moves
+        return x_a
+    x_b = torch.empty_like(x_a)
+    check(_lib().ngp_mesh_smooth(_ptr(x_a), _ptr(x_b), _ptr(vertices), _ptr(row_start), _ptr(neighbours), _ptr(multiplicity),
+                                 _ptr(vertex_flags), _ptr(fixed), n_vertices, int(neighbours.shape[0]), iterations, lam, mu,
+                                 MESH_SMOOTH_MODES[boundary], (ctypes.c_float * 3)(*move.tolist()), _stream()), "ngp_mesh_smooth")
+    return x_a if passes % 2 == 0 else x_b
+
+
+def mesh_vertex_normals(vertices, faces):
+    """Area-weighted vertex normals f32 [V,3] (csrc/mesh_smooth.hip): the f64 sum of the area vectors of a vertex's good faces in the
+    order of the stably sorted incidence list, normalised; 0 where the sum is 0 or not finite.  No host read."""
+    n_faces, n_vertices = _mesh_smooth_sizes(vertices, faces)
+    dev = vertices.device
+    normals = torch.zeros(n_vertices, 3, device=dev, dtype=torch.float32)
+    if n_faces == 0 or n_vertices == 0:
+        return normals
+    keys = torch.empty(3 * n_faces, device=dev, dtype=torch.int64)
+    check(_lib().ngp_mesh_vertex_normals_keys(_ptr(faces), n_faces, n_vertices, _ptr(keys), _stream()), "ngp_mesh_vertex_normals_keys")
+    keys, order = torch.sort(keys, stable=True)
+    check(_lib().ngp_mesh_vertex_normals(_ptr(vertices), _ptr(faces), n_faces, n_vertices, _ptr(keys), _ptr(order), _ptr(normals),
+                                         _stream()), "ngp_mesh_vertex_normals")
+    return normals
+
+
 # ---------------------------------------------------------------------------------------------------- surface rendering
 def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
     _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
