@@ -18,50 +18,50 @@
 // The skip tests (`changed[r - 1] == 0`, `changed[r] == 0`) read flags of EARLIER launches only.
 //
 //   cc_mark_kernel, cc_root_kernel, mesh_scan (mesh_scan.h), cc_assign_*_kernel   used vertices, root flags, the exclusive scan of the
-//                       flags (a wave per 512 slots, one block over the chunk totals, the wave walk again) and the labels
+//                       flags (a wave per 512 slots, one block over the chunk totals, the wave walk again) and the labels; bad faces
+//                       and unused vertices are counted by mesh_wave_count
 //   cc_edge_keys_kernel, cc_tally_*_kernel, cc_edge_kernel, cc_euler_kernel   the integer columns of the table: integer atomics,
 //                       aggregated in the wave: one atomic per distinct component among its lanes (one component usually owns
 //                       almost everything)
 //   cc_measure_block_kernel, cc_measure_final_kernel   area, volume and box in a fixed order: faces sorted by (component, index) are
 //                       cut into blocks of 64 per component, a wave sums a block by an xor tree, a wave sums a component's blocks
 //                       (lane l takes l, l + 64, ... in order, then the same tree).  No float atomics: two runs write the same bytes.
-//   cc_select_*_kernel  keep flags, the same scan, and the gather through the two maps
+//   cc_select_*_kernel, mesh_reindex_faces_kernel   keep flags, the same scan, and the gather through the two maps
+//
+// From mesh_edit.h: MESH_NO_KEY, mesh_face_indices with mesh_face_in_range (a good face here: a repeated index still joins; only the edge
+// keys ask for mesh_face_distinct), MeshCarve (the workspace, cc_workspace), mesh_wave_count, mesh_run_head, mesh_area_vector,
+// mesh_wave_sum, mesh_reindex_faces_kernel, mesh_blocks.
 //
 // Only integer atomicMin / atomicAdd and flag stores cross workgroups; their results do not depend on arrival order.
 #include "ngp_device.h"
-#include "mesh_scan.h"
+#include "mesh_edit.h"
 
 namespace ngp {
 
 constexpr int CC_BLOCK = 64;               // faces per block of the float sums: one per lane
 constexpr int CC_COLS = 6;                 // int columns of the table: vertices, faces, edges, boundary, non-manifold, euler
-constexpr long long CC_NO_EDGE = 0x7fffffffffffffffll;      // the key of an edge that does not count: sorts behind every real key
 
 struct CcPartial { double area, volume; int32_t lo[3], hi[3]; };         // 40 bytes; lo / hi as ordered keys (cc_key)
 
-__host__ __device__ __forceinline__ long long cc_chunks(long long n) { return mesh_scan_chunks(n); }
-__host__ __device__ __forceinline__ long long cc_align16(long long b) { return (b + 15) & ~15ll; }
 struct CcWorkspace {
     uint8_t* flags;       // [max(V, T)]: bit 0 used / kept, bit 1 root
     int32_t* chunk;       // [chunks(max(V, T))]: flagged slots per chunk, after the scan the index the chunk's first one gets
     int32_t* root_id;     // [V]: the number of the component whose root this vertex is, else -1
+    long long bytes;
 };
-__host__ __forceinline__ CcWorkspace cc_workspace(void* base, long long n_faces, long long n_vertices) {
+static CcWorkspace cc_workspace(void* base, long long n_faces, long long n_vertices) {
     const long long n = n_faces > n_vertices ? n_faces : n_vertices;
-    char* p = (char*)base;
+    MeshCarve c{(char*)base, 0};
     CcWorkspace w;
-    w.flags = (uint8_t*)p;     p += cc_align16(n);
-    w.chunk = (int32_t*)p;     p += cc_align16(4 * cc_chunks(n));
-    w.root_id = (int32_t*)p;
+    w.flags = c.take<uint8_t>(n);
+    w.chunk = c.take<int32_t>(mesh_scan_chunks(n));
+    w.root_id = c.take<int32_t>(n_vertices);
+    w.bytes = c.used;
     return w;
 }
 
 // a float's bits as an int that orders like the float, -0 below +0; its own inverse
 __device__ __forceinline__ int32_t cc_key(int32_t bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
-
-__device__ __forceinline__ bool cc_good(int a, int b, int c, int n_vertices) {
-    return (unsigned)a < (unsigned)n_vertices && (unsigned)b < (unsigned)n_vertices && (unsigned)c < (unsigned)n_vertices;
-}
 
 // the walk to the root.  Ends for ANY contents of parent[]: it goes on only to a strictly smaller non-negative index.
 __device__ __forceinline__ int cc_find(const int32_t* parent, int x) {
@@ -77,9 +77,10 @@ __global__ void __launch_bounds__(256) cc_hook_kernel(const int32_t* __restrict_
     if (r > 0 && changed[r - 1] == 0) return;              // the pass before this one (an earlier launch) already changed nothing
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= n_faces) return;
-    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    if (!cc_good(a, b, c, n_vertices)) return;
-    const int ra = cc_find(parent, a), rb = cc_find(parent, b), rc = cc_find(parent, c);
+    int idx[3];
+    mesh_face_indices(faces, f, idx);
+    if (!mesh_face_in_range(idx, n_vertices)) return;
+    const int ra = cc_find(parent, idx[0]), rb = cc_find(parent, idx[1]), rc = cc_find(parent, idx[2]);
     const int m = min(ra, min(rb, rc));
     if (ra != m) atomicMin(&parent[ra], m);
     if (rb != m && rb != ra) atomicMin(&parent[rb], m);
@@ -98,10 +99,14 @@ __global__ void __launch_bounds__(256) cc_compress_kernel(int n_vertices, int32_
 __global__ void __launch_bounds__(256) cc_mark_kernel(const int32_t* __restrict__ faces, int n_faces, int n_vertices, uint8_t* flags,
                                                       int32_t* counts) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (f >= n_faces) return;
-    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    if (cc_good(a, b, c, n_vertices)) flags[a] = flags[b] = flags[c] = 1;
-    else atomicAdd(&counts[1], 1);
+    bool bad = false;
+    if (f < n_faces) {
+        int idx[3];
+        mesh_face_indices(faces, f, idx);
+        bad = !mesh_face_in_range(idx, n_vertices);
+        if (!bad) flags[idx[0]] = flags[idx[1]] = flags[idx[2]] = 1;
+    }
+    mesh_wave_count(&counts[1], bad, threadIdx.x & 63);
 }
 
 __global__ void __launch_bounds__(256) cc_root_kernel(int n_vertices, const int32_t* __restrict__ parent, uint8_t* flags) {
@@ -114,11 +119,13 @@ __global__ void __launch_bounds__(256) cc_assign_vertices_kernel(int n_vertices,
                                                                  const uint8_t* __restrict__ flags, const int32_t* __restrict__ root_id,
                                                                  int32_t* __restrict__ vertex_component, int32_t* counts) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (v >= n_vertices) return;
-    const bool used = flags[v] != 0;
-    const int p = parent[v];
-    vertex_component[v] = used && (unsigned)p <= (unsigned)v ? root_id[p] : -1;
-    if (!used) atomicAdd(&counts[2], 1);
+    bool unused = false;
+    if (v < n_vertices) {
+        unused = flags[v] == 0;
+        const int p = parent[v];
+        vertex_component[v] = !unused && (unsigned)p <= (unsigned)v ? root_id[p] : -1;
+    }
+    mesh_wave_count(&counts[2], unused, threadIdx.x & 63);
 }
 
 __global__ void __launch_bounds__(256) cc_assign_faces_kernel(const int32_t* __restrict__ faces, int n_faces, int n_vertices,
@@ -126,8 +133,9 @@ __global__ void __launch_bounds__(256) cc_assign_faces_kernel(const int32_t* __r
                                                               int32_t* __restrict__ face_component) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= n_faces) return;
-    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    face_component[f] = cc_good(a, b, c, n_vertices) ? vertex_component[a] : -1;
+    int idx[3];
+    mesh_face_indices(faces, f, idx);
+    face_component[f] = mesh_face_in_range(idx, n_vertices) ? vertex_component[idx[0]] : -1;
 }
 
 // ---- the integer columns of the table --------------------------------------------------------------------------------------------------
@@ -153,25 +161,26 @@ __global__ void __launch_bounds__(256) cc_tally_kernel(const int32_t* __restrict
     cc_wave_add(table, col, comp, (unsigned)comp < (unsigned)n_components, threadIdx.x & 63);
 }
 
-// three keys per face, lo V + hi; CC_NO_EDGE for a bad face and for a face that repeats an index
+// three keys per face, lo V + hi; MESH_NO_KEY for a bad face and for a face that repeats an index
 __global__ void __launch_bounds__(256) cc_edge_keys_kernel(const int32_t* __restrict__ faces, int n_faces, int n_vertices,
                                                            long long* __restrict__ keys) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= n_faces) return;
-    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    const bool counts = cc_good(a, b, c, n_vertices) && a != b && b != c && c != a;
-    const int u[3] = {a, b, c}, w[3] = {b, c, a};
+    int u[3];
+    mesh_face_indices(faces, f, u);
+    const bool counts = mesh_face_distinct(u, n_vertices);
+    const int w[3] = {u[1], u[2], u[0]};
 #pragma unroll
     for (int k = 0; k < 3; ++k)
-        keys[3 * f + k] = counts ? (long long)min(u[k], w[k]) * n_vertices + max(u[k], w[k]) : CC_NO_EDGE;
+        keys[3 * f + k] = counts ? (long long)min(u[k], w[k]) * n_vertices + max(u[k], w[k]) : MESH_NO_KEY;
 }
 
 // over the SORTED keys: the first of a run of equal keys is the edge; it looks at most two slots ahead (used once, twice, more)
 __global__ void __launch_bounds__(256) cc_edge_kernel(const long long* __restrict__ keys, long long n, int n_vertices, int n_components,
                                                       const int32_t* __restrict__ vertex_component, int32_t* table) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long k = i < n ? keys[i] : CC_NO_EDGE;
-    bool head = k != CC_NO_EDGE && k >= 0 && (i == 0 || keys[i - 1] != k);
+    const long long k = i < n ? keys[i] : MESH_NO_KEY;
+    bool head = k != MESH_NO_KEY && k >= 0 && mesh_run_head(keys, i);
     int comp = -1;
     bool twice = false, more = false;
     if (head) {
@@ -195,10 +204,10 @@ __global__ void __launch_bounds__(256) cc_euler_kernel(int n_components, int32_t
 
 // ---- area, volume, box -----------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void cc_wave_reduce(CcPartial& p) {
+    p.area = mesh_wave_sum(p.area);
+    p.volume = mesh_wave_sum(p.volume);
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
-        p.area += __shfl_xor(p.area, d, 64);
-        p.volume += __shfl_xor(p.volume, d, 64);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             p.lo[k] = min(p.lo[k], __shfl_xor(p.lo[k], d, 64));
@@ -227,20 +236,18 @@ __global__ void __launch_bounds__(256) cc_measure_block_kernel(const float* __re
     if (pos < face_start[lo + 1] && pos < n_faces) {
         const long long f = order[pos];
         if (f >= 0 && f < n_faces) {
-            const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-            if (cc_good(ia, ib, ic, n_vertices)) {
-                double a[3], b[3], c[3];
+            int idx[3];
+            mesh_face_indices(faces, f, idx);
+            if (mesh_face_in_range(idx, n_vertices)) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    const float fa = vertices[3ll * ia + k], fb = vertices[3ll * ib + k], fc = vertices[3ll * ic + k];
-                    a[k] = fa; b[k] = fb; c[k] = fc;
+                    const float fa = vertices[3ll * idx[0] + k], fb = vertices[3ll * idx[1] + k], fc = vertices[3ll * idx[2] + k];
                     const int32_t ka = cc_key(__float_as_int(fa)), kb = cc_key(__float_as_int(fb)), kc = cc_key(__float_as_int(fc));
                     p.lo[k] = min(ka, min(kb, kc));
                     p.hi[k] = max(ka, max(kb, kc));
                 }
-                const double u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, w[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-                const double n[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
-                p.area = 0.5 * sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+                double a[3], b[3], c[3], nn[3];
+                p.area = 0.5 * sqrt(mesh_area_vector(vertices, idx, a, b, c, nn));
                 const double bc[3] = {b[1] * c[2] - b[2] * c[1], b[2] * c[0] - b[0] * c[2], b[0] * c[1] - b[1] * c[0]};
                 p.volume = (a[0] * bc[0] + a[1] * bc[1] + a[2] * bc[2]) / 6.0;
             }
@@ -300,37 +307,15 @@ __global__ void __launch_bounds__(256) cc_select_vertices_kernel(const float* __
     }
 }
 
-__global__ void __launch_bounds__(256) cc_select_faces_kernel(const int32_t* __restrict__ faces, int n_faces, int n_vertices,
-                                                              const int32_t* __restrict__ vertex_map, const int32_t* __restrict__ face_map,
-                                                              int n_out, int32_t* __restrict__ out_faces) {
-    const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (f >= n_faces) return;
-    const int m = face_map[f];
-    if ((unsigned)m >= (unsigned)n_out) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int v = faces[3 * f + k];
-        out_faces[3ll * m + k] = (unsigned)v < (unsigned)n_vertices ? vertex_map[v] : -1;      // a kept face is a good face
-    }
-}
-
 }  // namespace ngp
 
 using namespace ngp;
-
-static unsigned cc_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
-
-// index[i] of the flagged slots of flags[0, n), their number to *total: three launches (mesh_scan.h)
-static void cc_scan(const CcWorkspace& w, int bit, long long n, int32_t* index, int32_t* total, hipStream_t s) {
-    mesh_scan(w.flags, bit, n, w.chunk, index, total, s);
-}
 
 extern "C" {
 
 long long ngp_mesh_components_bytes(int n_faces, int n_vertices) {
     if (n_faces < 1 || n_vertices < 1) return -1;
-    const long long n = n_faces > n_vertices ? n_faces : n_vertices;
-    return cc_align16(n) + cc_align16(4 * cc_chunks(n)) + cc_align16(4ll * n_vertices);
+    return cc_workspace(nullptr, n_faces, n_vertices).bytes;
 }
 
 int ngp_mesh_components_rounds(const int32_t* faces, int n_faces, int n_vertices, int32_t* parent, int32_t* changed, int n_rounds,
@@ -338,8 +323,8 @@ int ngp_mesh_components_rounds(const int32_t* faces, int n_faces, int n_vertices
     if (!faces || !parent || !changed || n_faces < 1 || n_vertices < 1 || n_rounds < 1) return -1;
     hipStream_t s = (hipStream_t)stream;
     for (int r = 0; r < n_rounds; ++r) {
-        hipLaunchKernelGGL(cc_hook_kernel, dim3(cc_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, parent, changed, r);
-        hipLaunchKernelGGL(cc_compress_kernel, dim3(cc_blocks(n_vertices, 256)), dim3(256), 0, s, n_vertices, parent, changed, r);
+        hipLaunchKernelGGL(cc_hook_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, parent, changed, r);
+        hipLaunchKernelGGL(cc_compress_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, n_vertices, parent, changed, r);
     }
     NGP_LAUNCH_CHECK();
     return 0;
@@ -353,12 +338,12 @@ int ngp_mesh_components_label(const int32_t* faces, int n_faces, int n_vertices,
     hipError_t e = hipMemsetAsync(w.flags, 0, (size_t)n_vertices, s);
     if (e == hipSuccess) e = hipMemsetAsync(counts, 0, 3 * sizeof(int32_t), s);
     if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(cc_mark_kernel, dim3(cc_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, w.flags, counts);
-    hipLaunchKernelGGL(cc_root_kernel, dim3(cc_blocks(n_vertices, 256)), dim3(256), 0, s, n_vertices, parent, w.flags);
-    cc_scan(w, 2, n_vertices, w.root_id, counts, s);
-    hipLaunchKernelGGL(cc_assign_vertices_kernel, dim3(cc_blocks(n_vertices, 256)), dim3(256), 0, s, n_vertices, parent, w.flags, w.root_id,
+    hipLaunchKernelGGL(cc_mark_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, w.flags, counts);
+    hipLaunchKernelGGL(cc_root_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, n_vertices, parent, w.flags);
+    mesh_scan(w.flags, 2, n_vertices, w.chunk, w.root_id, counts, s);
+    hipLaunchKernelGGL(cc_assign_vertices_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, n_vertices, parent, w.flags, w.root_id,
                        vertex_component, counts);
-    hipLaunchKernelGGL(cc_assign_faces_kernel, dim3(cc_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_component,
+    hipLaunchKernelGGL(cc_assign_faces_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_component,
                        face_component);
     NGP_LAUNCH_CHECK();
     return 0;
@@ -366,7 +351,7 @@ int ngp_mesh_components_label(const int32_t* faces, int n_faces, int n_vertices,
 
 int ngp_mesh_components_edge_keys(const int32_t* faces, int n_faces, int n_vertices, int64_t* keys, void* stream) {
     if (!faces || !keys || n_faces < 1 || n_vertices < 1) return -1;
-    hipLaunchKernelGGL(cc_edge_keys_kernel, dim3(cc_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream, faces, n_faces, n_vertices,
+    hipLaunchKernelGGL(cc_edge_keys_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream, faces, n_faces, n_vertices,
                        (long long*)keys);
     NGP_LAUNCH_CHECK();
     return 0;
@@ -378,13 +363,13 @@ int ngp_mesh_components_table(int n_faces, int n_vertices, const int32_t* vertex
     hipStream_t s = (hipStream_t)stream;
     const hipError_t e = hipMemsetAsync(table, 0, (size_t)n_components * CC_COLS * sizeof(int32_t), s);
     if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(cc_tally_kernel, dim3(cc_blocks(n_vertices, 256)), dim3(256), 0, s, vertex_component, (long long)n_vertices,
+    hipLaunchKernelGGL(cc_tally_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, vertex_component, (long long)n_vertices,
                        n_components, 0, table);
-    hipLaunchKernelGGL(cc_tally_kernel, dim3(cc_blocks(n_faces, 256)), dim3(256), 0, s, face_component, (long long)n_faces, n_components, 1,
+    hipLaunchKernelGGL(cc_tally_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, face_component, (long long)n_faces, n_components, 1,
                        table);
-    hipLaunchKernelGGL(cc_edge_kernel, dim3(cc_blocks(3ll * n_faces, 256)), dim3(256), 0, s, (const long long*)sorted_keys, 3ll * n_faces,
+    hipLaunchKernelGGL(cc_edge_kernel, dim3(mesh_blocks(3ll * n_faces, 256)), dim3(256), 0, s, (const long long*)sorted_keys, 3ll * n_faces,
                        n_vertices, n_components, vertex_component, table);
-    hipLaunchKernelGGL(cc_euler_kernel, dim3(cc_blocks(n_components, 256)), dim3(256), 0, s, n_components, table);
+    hipLaunchKernelGGL(cc_euler_kernel, dim3(mesh_blocks(n_components, 256)), dim3(256), 0, s, n_components, table);
     NGP_LAUNCH_CHECK();
     return 0;
 }
@@ -401,9 +386,9 @@ int ngp_mesh_components_measure(const float* vertices, const int32_t* faces, con
     if (ngp_mesh_components_partial_bytes(n_faces, n_components) < 0 || n_vertices < 1) return -1;
     hipStream_t s = (hipStream_t)stream;
     const long long blocks = (long long)n_faces / CC_BLOCK + n_components;            // sum of ceil(n_c / 64) is at most this
-    hipLaunchKernelGGL(cc_measure_block_kernel, dim3(cc_blocks(blocks, 4)), dim3(256), 0, s, vertices, faces, (const long long*)order,
+    hipLaunchKernelGGL(cc_measure_block_kernel, dim3(mesh_blocks(blocks, 4)), dim3(256), 0, s, vertices, faces, (const long long*)order,
                        n_faces, n_vertices, face_start, block_start, n_components, (CcPartial*)partials);
-    hipLaunchKernelGGL(cc_measure_final_kernel, dim3(cc_blocks(n_components, 4)), dim3(256), 0, s, (const CcPartial*)partials, block_start,
+    hipLaunchKernelGGL(cc_measure_final_kernel, dim3(mesh_blocks(n_components, 4)), dim3(256), 0, s, (const CcPartial*)partials, block_start,
                        n_components, area, volume, lo, hi);
     NGP_LAUNCH_CHECK();
     return 0;
@@ -416,12 +401,12 @@ int ngp_mesh_select_count(int n_faces, int n_vertices, const int32_t* vertex_com
     if (n_faces < 1 || n_vertices < 1 || n_components < 1) return -1;
     const CcWorkspace w = cc_workspace(workspace, n_faces, n_vertices);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(cc_select_flags_kernel, dim3(cc_blocks(n_vertices, 256)), dim3(256), 0, s, vertex_component, (long long)n_vertices,
+    hipLaunchKernelGGL(cc_select_flags_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, vertex_component, (long long)n_vertices,
                        keep, n_components, w.flags);
-    cc_scan(w, 1, n_vertices, vertex_map, counts, s);
-    hipLaunchKernelGGL(cc_select_flags_kernel, dim3(cc_blocks(n_faces, 256)), dim3(256), 0, s, face_component, (long long)n_faces, keep,
+    mesh_scan(w.flags, 1, n_vertices, w.chunk, vertex_map, counts, s);
+    hipLaunchKernelGGL(cc_select_flags_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, face_component, (long long)n_faces, keep,
                        n_components, w.flags);
-    cc_scan(w, 1, n_faces, face_map, counts + 1, s);
+    mesh_scan(w.flags, 1, n_faces, w.chunk, face_map, counts + 1, s);
     NGP_LAUNCH_CHECK();
     return 0;
 }
@@ -432,9 +417,9 @@ int ngp_mesh_select_emit(const float* vertices, const float* normals, const int3
     if (!vertices || !faces || !vertex_map || !face_map || !out_vertices || !out_faces || (normals && !out_normals)) return -1;
     if (n_faces < 1 || n_vertices < 1 || n_out_vertices < 1 || n_out_faces < 1) return -1;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(cc_select_vertices_kernel, dim3(cc_blocks(n_vertices, 256)), dim3(256), 0, s, vertices, normals, n_vertices,
+    hipLaunchKernelGGL(cc_select_vertices_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, vertices, normals, n_vertices,
                        vertex_map, n_out_vertices, out_vertices, out_normals);
-    hipLaunchKernelGGL(cc_select_faces_kernel, dim3(cc_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_map,
+    hipLaunchKernelGGL(mesh_reindex_faces_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_map,
                        face_map, n_out_faces, out_faces);
     NGP_LAUNCH_CHECK();
     return 0;

@@ -4,8 +4,8 @@
 //
 //   ms_keys_kernel            a lane per vertex: the cell key (f32 subtract, multiply, floorf, clamp; exact int64 after that)
 //       torch.sort (stable) of the V keys: plumbing
-//   ms_heads_kernel, mesh_scan<true>, ms_cluster_kernel    the first slot of every run of equal keys, the run number of every slot,
-//                             vertex_cluster through the sort's permutation
+//   mesh_number_runs, ms_cluster_kernel                    the first slot of every run of equal keys, the run number of every slot
+//                             (mesh_edit.h: mesh_run_heads_kernel, mesh_scan<true>), vertex_cluster through the sort's permutation
 //   ms_faces_kernel           a lane per face: bad / survives; marks the clusters a surviving face names
 //   mesh_scan x 2, ms_vertex_map_kernel                      face_map, the number of every marked cluster, vertex_map
 //       ONE host read: {clusters, V', T', bad vertices, bad faces}
@@ -15,44 +15,38 @@
 //   ms_solve_kernel           a WAVE per output vertex: lane l adds the terms l, l + 64, ... of the cluster's run in that order (twelve
 //                             f64 sums per incidence, three per vertex), an xor tree over the 64 lanes, lane 0 solves the 3 x 3 system
 //                             (LDL^T, the matrix is positive definite with condition <= (1 + eps) / eps) and writes position and normal
-//   ms_emit_faces_kernel      a lane per face: the surviving faces through the two maps
+//   mesh_reindex_faces_kernel a lane per face: the surviving faces through the two maps
+//
+// From mesh_edit.h: MESH_NO_KEY, mesh_face_indices with mesh_face_in_range (a face that repeats an index is no bad face here: it has no
+// area and does not survive), MeshCarve (the workspace, ms_workspace), mesh_wave_count, mesh_run_head / mesh_run_tail, mesh_number_runs,
+// mesh_area_vector, mesh_wave_sum, mesh_reindex_faces_kernel, mesh_blocks.
 //
 // No float atomics: a sum's order depends on the sorted list alone, so two runs write the same bytes and a bad face elsewhere in the list
 // moves no bit.  Integer atomics count the bad vertices and faces (one per wave); flag stores of the same value may race.
 #include "ngp_device.h"
-#include "mesh_scan.h"
+#include "mesh_edit.h"
 
 namespace ngp {
 
-constexpr long long MS_NO_KEY = 0x7fffffffffffffffll;      // a bad vertex, a corner that does not count: sorts behind every real key
 constexpr int MS_MAX_CELLS = 1 << 21;                      // per axis: three of them fit 63 bits (not all three at once: ms_grid)
 
 struct MsGrid { float lo[3], inv_h[3], h[3]; int n[3]; };
 enum { MS_CLUSTERS = 0, MS_OUT_VERTICES = 1, MS_OUT_FACES = 2, MS_BAD_VERTICES = 3, MS_BAD_FACES = 4, MS_COUNTS = 5 };
 
-__host__ __device__ __forceinline__ long long ms_align16(long long b) { return (b + 15) & ~15ll; }
 struct MsWorkspace {
     uint8_t* vertex_flags;    // [V]: over sorted slots the first of a run; later, over cluster numbers, named by a surviving face
     uint8_t* face_flags;      // [T]: survives
     int32_t* chunk;           // [chunks(max(V, T))]
+    long long bytes;
 };
-__host__ __forceinline__ MsWorkspace ms_workspace(void* base, long long n_faces, long long n_vertices) {
-    char* p = (char*)base;
+static MsWorkspace ms_workspace(void* base, long long n_faces, long long n_vertices) {
+    MeshCarve c{(char*)base, 0};
     MsWorkspace w;
-    w.vertex_flags = (uint8_t*)p;   p += ms_align16(n_vertices);
-    w.face_flags = (uint8_t*)p;     p += ms_align16(n_faces);
-    w.chunk = (int32_t*)p;
+    w.vertex_flags = c.take<uint8_t>(n_vertices);
+    w.face_flags = c.take<uint8_t>(n_faces);
+    w.chunk = c.take<int32_t>(mesh_scan_chunks(n_faces > n_vertices ? n_faces : n_vertices));
+    w.bytes = c.used;
     return w;
-}
-
-__device__ __forceinline__ bool ms_index_ok(int a, int b, int c, int n_vertices) {
-    return (unsigned)a < (unsigned)n_vertices && (unsigned)b < (unsigned)n_vertices && (unsigned)c < (unsigned)n_vertices;
-}
-
-// counts[slot] += the number of lanes with `on`; every lane of the wave calls it
-__device__ __forceinline__ void ms_wave_count(int32_t* counts, int slot, bool on, int lane) {
-    const unsigned long long m = __ballot(on);
-    if (m && lane == __ffsll((long long)m) - 1) atomicAdd(&counts[slot], __popcll(m));
 }
 
 __global__ void __launch_bounds__(256) ms_keys_kernel(const float* __restrict__ vertices, int n_vertices, MsGrid g,
@@ -71,16 +65,9 @@ __global__ void __launch_bounds__(256) ms_keys_kernel(const float* __restrict__ 
             c = c < top ? c : top;
             q[k] = (long long)c;
         }
-        keys[v] = bad ? MS_NO_KEY : q[0] + (long long)g.n[0] * (q[1] + (long long)g.n[1] * q[2]);
+        keys[v] = bad ? MESH_NO_KEY : q[0] + (long long)g.n[0] * (q[1] + (long long)g.n[1] * q[2]);
     }
-    ms_wave_count(counts, MS_BAD_VERTICES, bad, threadIdx.x & 63);
-}
-
-__global__ void __launch_bounds__(256) ms_heads_kernel(const long long* __restrict__ sorted_keys, int n_vertices, uint8_t* __restrict__ flags) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_vertices) return;
-    const long long k = sorted_keys[i];
-    flags[i] = k != MS_NO_KEY && (i == 0 || sorted_keys[i - 1] != k) ? 1 : 0;
+    mesh_wave_count(&counts[MS_BAD_VERTICES], bad, threadIdx.x & 63);
 }
 
 __global__ void __launch_bounds__(256) ms_cluster_kernel(const long long* __restrict__ sorted_keys, const long long* __restrict__ order,
@@ -89,14 +76,14 @@ __global__ void __launch_bounds__(256) ms_cluster_kernel(const long long* __rest
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_vertices) return;
     const long long v = order[i];
-    if (v >= 0 && v < n_vertices) vertex_cluster[v] = sorted_keys[i] != MS_NO_KEY ? run[i] : -1;
+    if (v >= 0 && v < n_vertices) vertex_cluster[v] = sorted_keys[i] != MESH_NO_KEY ? run[i] : -1;
 }
 
 // the clusters of a face's corners; false for a bad face (an index outside [0, V) or a bad vertex)
 __device__ __forceinline__ bool ms_face_clusters(const int32_t* __restrict__ faces, long long f, int n_vertices,
                                                  const int32_t* __restrict__ vertex_cluster, int idx[3], int cl[3]) {
-    idx[0] = faces[3 * f]; idx[1] = faces[3 * f + 1]; idx[2] = faces[3 * f + 2];
-    if (!ms_index_ok(idx[0], idx[1], idx[2], n_vertices)) return false;
+    mesh_face_indices(faces, f, idx);
+    if (!mesh_face_in_range(idx, n_vertices)) return false;
     cl[0] = vertex_cluster[idx[0]]; cl[1] = vertex_cluster[idx[1]]; cl[2] = vertex_cluster[idx[2]];
     return cl[0] >= 0 && cl[1] >= 0 && cl[2] >= 0;
 }
@@ -113,7 +100,7 @@ __global__ void __launch_bounds__(256) ms_faces_kernel(const int32_t* __restrict
         face_flags[f] = survives ? 1 : 0;
         if (survives) cluster_flags[cl[0]] = cluster_flags[cl[1]] = cluster_flags[cl[2]] = 1;      // cl < clusters <= V
     }
-    ms_wave_count(counts, MS_BAD_FACES, bad, threadIdx.x & 63);
+    mesh_wave_count(&counts[MS_BAD_FACES], bad, threadIdx.x & 63);
 }
 
 __global__ void __launch_bounds__(256) ms_vertex_map_kernel(const int32_t* __restrict__ vertex_cluster, const int32_t* __restrict__ cluster_out,
@@ -124,22 +111,7 @@ __global__ void __launch_bounds__(256) ms_vertex_map_kernel(const int32_t* __res
     vertex_map[v] = (unsigned)c < (unsigned)n_vertices ? cluster_out[c] : -1;
 }
 
-// the face's corners in f64 and its doubled area vector nn = (b - a) x (c - a), every product and difference a rounding of its own;
-// returns |nn|^2, and the face has area iff that is > 0 (the keys and the sums decide it by this one function)
-__device__ __forceinline__ double ms_area_vector(const float* __restrict__ vertices, const int idx[3], double a[3], double nn[3]) {
-    double u[3], w[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        a[k] = (double)vertices[3ll * idx[0] + k];
-        u[k] = (double)vertices[3ll * idx[1] + k] - a[k];
-        w[k] = (double)vertices[3ll * idx[2] + k] - a[k];
-    }
-    nn[0] = u[1] * w[2] - u[2] * w[1];
-    nn[1] = u[2] * w[0] - u[0] * w[2];
-    nn[2] = u[0] * w[1] - u[1] * w[0];
-    return (nn[0] * nn[0] + nn[1] * nn[1]) + nn[2] * nn[2];
-}
-
+// the keys and the sums decide "the face has area" by the one mesh_area_vector(...) > 0
 __global__ void __launch_bounds__(256) ms_incidence_keys_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
                                                                 int n_faces, int n_vertices, const int32_t* __restrict__ vertex_cluster,
                                                                 long long* __restrict__ keys) {
@@ -148,12 +120,12 @@ __global__ void __launch_bounds__(256) ms_incidence_keys_kernel(const float* __r
     int idx[3], cl[3];
     bool counts = ms_face_clusters(faces, f, n_vertices, vertex_cluster, idx, cl);
     if (counts) {
-        double a[3], nn[3];
-        counts = ms_area_vector(vertices, idx, a, nn) > 0.0;
+        double a[3], b[3], c[3], nn[3];
+        counts = mesh_area_vector(vertices, idx, a, b, c, nn) > 0.0;
     }
-    keys[3 * f] = counts ? (long long)cl[0] : MS_NO_KEY;
-    keys[3 * f + 1] = counts && cl[1] != cl[0] ? (long long)cl[1] : MS_NO_KEY;
-    keys[3 * f + 2] = counts && cl[2] != cl[0] && cl[2] != cl[1] ? (long long)cl[2] : MS_NO_KEY;
+    keys[3 * f] = counts ? (long long)cl[0] : MESH_NO_KEY;
+    keys[3 * f + 1] = counts && cl[1] != cl[0] ? (long long)cl[1] : MESH_NO_KEY;
+    keys[3 * f + 2] = counts && cl[2] != cl[0] && cl[2] != cl[1] ? (long long)cl[2] : MESH_NO_KEY;
 }
 
 // runs: int32 [4 C + V']: vertex run start [C], end [C], incidence run start [C], end [C] (zeroed: a cluster without incidences has the
@@ -165,17 +137,17 @@ __global__ void __launch_bounds__(256) ms_vertex_runs_kernel(const long long* __
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_vertices) return;
     const long long k = sorted_keys[i];
-    if (k == MS_NO_KEY) return;
+    if (k == MESH_NO_KEY) return;
     const long long v = order[i];
     if (v < 0 || v >= n_vertices) return;
     const int c = vertex_cluster[v];
     if ((unsigned)c >= (unsigned)n_clusters) return;
-    if (i == 0 || sorted_keys[i - 1] != k) {
+    if (mesh_run_head(sorted_keys, i)) {
         runs[c] = (int)i;
         const int o = cluster_out[c];
         if ((unsigned)o < (unsigned)n_out) runs[4ll * n_clusters + o] = c;
     }
-    if (i + 1 == n_vertices || sorted_keys[i + 1] != k) runs[(long long)n_clusters + c] = (int)i + 1;
+    if (mesh_run_tail(sorted_keys, i, n_vertices)) runs[(long long)n_clusters + c] = (int)i + 1;
 }
 
 __global__ void __launch_bounds__(256) ms_incidence_runs_kernel(const long long* __restrict__ sorted_keys, long long n, int n_clusters,
@@ -183,9 +155,9 @@ __global__ void __launch_bounds__(256) ms_incidence_runs_kernel(const long long*
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const long long k = sorted_keys[i];
-    if (k < 0 || k >= n_clusters) return;                                   // MS_NO_KEY
-    if (i == 0 || sorted_keys[i - 1] != k) runs[2ll * n_clusters + k] = (int)i;
-    if (i + 1 == n || sorted_keys[i + 1] != k) runs[3ll * n_clusters + k] = (int)i + 1;
+    if (k < 0 || k >= n_clusters) return;                                   // MESH_NO_KEY
+    if (mesh_run_head(sorted_keys, i)) runs[2ll * n_clusters + k] = (int)i;
+    if (mesh_run_tail(sorted_keys, i, n)) runs[3ll * n_clusters + k] = (int)i + 1;
 }
 
 constexpr int MS_SUMS = 15;      // A (6: xx xy xz yy yz zz), b (3), area vector (3), sum of v - c (3)
@@ -220,10 +192,10 @@ __global__ void __launch_bounds__(256) ms_solve_kernel(const float* __restrict__
         const long long f = inc_order[i] / 3;
         if (f < 0 || f >= n_faces) continue;
         int idx[3];
-        idx[0] = faces[3 * f]; idx[1] = faces[3 * f + 1]; idx[2] = faces[3 * f + 2];
-        if (!ms_index_ok(idx[0], idx[1], idx[2], n_vertices)) continue;
-        double a[3], nn[3];
-        const double len2 = ms_area_vector(vertices, idx, a, nn);
+        mesh_face_indices(faces, f, idx);
+        if (!mesh_face_in_range(idx, n_vertices)) continue;
+        double a[3], b[3], c[3], nn[3];
+        const double len2 = mesh_area_vector(vertices, idx, a, b, c, nn);
         if (!(len2 > 0.0)) continue;
         const double len = sqrt(len2), w = 0.5 * len;
         const double n[3] = {nn[0] / len, nn[1] / len, nn[2] / len};
@@ -243,10 +215,7 @@ __global__ void __launch_bounds__(256) ms_solve_kernel(const float* __restrict__
         for (int k = 0; k < 3; ++k) s[12 + k] += (double)vertices[3 * v + k] - centre[k];
     }
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int j = 0; j < MS_SUMS; ++j) s[j] += __shfl_xor(s[j], d, 64);
-    }
+    for (int j = 0; j < MS_SUMS; ++j) s[j] = mesh_wave_sum(s[j]);
     if (lane != 0) return;
     const double count = (double)(v1 - v0);
     double y[3] = {s[12] / count, s[13] / count, s[14] / count};           // the mean: the answer without a quadric
@@ -280,25 +249,9 @@ __global__ void __launch_bounds__(256) ms_solve_kernel(const float* __restrict__
     }
 }
 
-__global__ void __launch_bounds__(256) ms_emit_faces_kernel(const int32_t* __restrict__ faces, int n_faces, int n_vertices,
-                                                            const int32_t* __restrict__ vertex_map, const int32_t* __restrict__ face_map,
-                                                            int n_out, int32_t* __restrict__ out_faces) {
-    const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (f >= n_faces) return;
-    const int m = face_map[f];
-    if ((unsigned)m >= (unsigned)n_out) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int v = faces[3 * f + k];
-        out_faces[3ll * m + k] = (unsigned)v < (unsigned)n_vertices ? vertex_map[v] : -1;          // a surviving face is a good face
-    }
-}
-
 }  // namespace ngp
 
 using namespace ngp;
-
-static unsigned ms_blocks(long long n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
 // the host's grid -> the kernels' argument; false where the contract refuses it
 static bool ms_grid(const float* lo, const float* inv_h, const float* h, const int32_t* n, MsGrid* g) {
@@ -308,7 +261,7 @@ static bool ms_grid(const float* lo, const float* inv_h, const float* h, const i
         if (n[k] < 1 || n[k] > MS_MAX_CELLS) return false;
         g->lo[k] = lo[k]; g->inv_h[k] = inv_h[k]; g->h[k] = h[k]; g->n[k] = n[k];
     }
-    // the last cell of a grid of 2^21 cells on every axis would have the key INT64_MAX, which is MS_NO_KEY
+    // the last cell of a grid of 2^21 cells on every axis would have the key INT64_MAX, which is MESH_NO_KEY
     return !(n[0] == MS_MAX_CELLS && n[1] == MS_MAX_CELLS && n[2] == MS_MAX_CELLS);
 }
 
@@ -316,8 +269,7 @@ extern "C" {
 
 long long ngp_mesh_simplify_bytes(int n_faces, int n_vertices) {
     if (n_faces < 0 || n_vertices < 1) return -1;
-    const long long n = n_faces > n_vertices ? n_faces : n_vertices;
-    return ms_align16(n_vertices) + ms_align16(n_faces) + ms_align16(4 * mesh_scan_chunks(n));
+    return ms_workspace(nullptr, n_faces, n_vertices).bytes;
 }
 
 int ngp_mesh_simplify_keys(const float* vertices, int n_vertices, const float* lo, const float* inv_h, const float* h, const int32_t* n,
@@ -327,7 +279,7 @@ int ngp_mesh_simplify_keys(const float* vertices, int n_vertices, const float* l
     hipStream_t s = (hipStream_t)stream;
     const hipError_t e = hipMemsetAsync(counts, 0, MS_COUNTS * sizeof(int32_t), s);
     if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(ms_keys_kernel, dim3(ms_blocks(n_vertices, 256)), dim3(256), 0, s, vertices, n_vertices, g, (long long*)keys, counts);
+    hipLaunchKernelGGL(ms_keys_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, vertices, n_vertices, g, (long long*)keys, counts);
     NGP_LAUNCH_CHECK();
     return 0;
 }
@@ -339,15 +291,15 @@ int ngp_mesh_simplify_count(const int32_t* faces, int n_faces, int n_vertices, c
     if (n_faces < 0 || n_vertices < 1 || (n_faces > 0 && (!faces || !face_map))) return -1;
     const MsWorkspace w = ms_workspace(workspace, n_faces, n_vertices);
     hipStream_t s = (hipStream_t)stream;
-    const unsigned vb = ms_blocks(n_vertices, 256);
-    hipLaunchKernelGGL(ms_heads_kernel, dim3(vb), dim3(256), 0, s, (const long long*)sorted_keys, n_vertices, w.vertex_flags);
-    mesh_scan<true>(w.vertex_flags, 1, n_vertices, w.chunk, vertex_map, counts + MS_CLUSTERS, s);       // vertex_map: scratch until the end
+    const unsigned vb = mesh_blocks(n_vertices, 256);
+    mesh_number_runs((const long long*)sorted_keys, n_vertices, w.vertex_flags, w.chunk, vertex_map /* scratch until the end */,
+                     counts + MS_CLUSTERS, s);
     hipLaunchKernelGGL(ms_cluster_kernel, dim3(vb), dim3(256), 0, s, (const long long*)sorted_keys, (const long long*)order, vertex_map,
                        n_vertices, vertex_cluster);
     const hipError_t e = hipMemsetAsync(w.vertex_flags, 0, (size_t)n_vertices, s);
     if (e != hipSuccess) return -(int)e;
     if (n_faces > 0) {
-        hipLaunchKernelGGL(ms_faces_kernel, dim3(ms_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_cluster,
+        hipLaunchKernelGGL(ms_faces_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_cluster,
                            w.face_flags, w.vertex_flags, counts);
         mesh_scan<false>(w.face_flags, 1, n_faces, w.chunk, face_map, counts + MS_OUT_FACES, s);
     }
@@ -360,7 +312,7 @@ int ngp_mesh_simplify_count(const int32_t* faces, int n_faces, int n_vertices, c
 int ngp_mesh_simplify_incidence_keys(const float* vertices, const int32_t* faces, int n_faces, int n_vertices,
                                      const int32_t* vertex_cluster, int64_t* keys, void* stream) {
     if (!vertices || !faces || !vertex_cluster || !keys || n_faces < 1 || n_vertices < 1) return -1;
-    hipLaunchKernelGGL(ms_incidence_keys_kernel, dim3(ms_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream, vertices, faces, n_faces,
+    hipLaunchKernelGGL(ms_incidence_keys_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream, vertices, faces, n_faces,
                        n_vertices, vertex_cluster, (long long*)keys);
     NGP_LAUNCH_CHECK();
     return 0;
@@ -388,14 +340,14 @@ int ngp_mesh_simplify_emit(const float* vertices, const int32_t* faces, int n_fa
     int32_t* r = (int32_t*)runs;
     const hipError_t e = hipMemsetAsync(r, 0, (size_t)ngp_mesh_simplify_runs_bytes(n_clusters, n_out_vertices), s);
     if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(ms_vertex_runs_kernel, dim3(ms_blocks(n_vertices, 256)), dim3(256), 0, s, (const long long*)vertex_keys,
+    hipLaunchKernelGGL(ms_vertex_runs_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, (const long long*)vertex_keys,
                        (const long long*)vertex_order, vertex_cluster, cluster_out, n_vertices, n_clusters, n_out_vertices, r);
-    hipLaunchKernelGGL(ms_incidence_runs_kernel, dim3(ms_blocks(3ll * n_faces, 256)), dim3(256), 0, s, (const long long*)incidence_keys,
+    hipLaunchKernelGGL(ms_incidence_runs_kernel, dim3(mesh_blocks(3ll * n_faces, 256)), dim3(256), 0, s, (const long long*)incidence_keys,
                        3ll * n_faces, n_clusters, r);
-    hipLaunchKernelGGL(ms_solve_kernel, dim3(ms_blocks(n_out_vertices, 4)), dim3(256), 0, s, vertices, faces, n_faces, n_vertices, g,
+    hipLaunchKernelGGL(ms_solve_kernel, dim3(mesh_blocks(n_out_vertices, 4)), dim3(256), 0, s, vertices, faces, n_faces, n_vertices, g,
                        (const long long*)vertex_keys, (const long long*)vertex_order, (const long long*)incidence_keys,
                        (const long long*)incidence_order, r, n_clusters, n_out_vertices, regularization, out_vertices, out_normals);
-    hipLaunchKernelGGL(ms_emit_faces_kernel, dim3(ms_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_map, face_map,
+    hipLaunchKernelGGL(mesh_reindex_faces_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, vertex_map, face_map,
                        n_out_faces, out_faces);
     NGP_LAUNCH_CHECK();
     return 0;

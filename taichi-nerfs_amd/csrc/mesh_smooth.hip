@@ -4,16 +4,21 @@
 //
 //   sm_edge_keys_kernel       a lane per face: six directed keys u V + w (both directions of the three edges), INT64_MAX for a bad face
 //       torch.sort of the 6 T keys: plumbing
-//   sm_heads_kernel, mesh_scan<true>     the first slot of every run of equal keys, the run number of every slot; the number of runs is E2
+//   mesh_number_runs          the first slot of every run of equal keys, the run number of every slot (mesh_edit.h: mesh_run_heads_kernel,
+//                             mesh_scan<true>); the number of runs is E2
 //   sm_build_kernel           a lane per slot: the head of run e writes neighbours[e] = key mod V and multiplicity[e] = the run's length,
 //                             walked forward and cut at 255
-//   sm_rows_kernel            a lane per row bound: row_start[v] = the run at the lower bound of v V in the sorted keys (a bisection)
+//   sm_rows_kernel            a lane per row bound: row_start[v] = the run at the lower bound of v V in the sorted keys (mesh_lower_bound)
 //   sm_vertex_flags_kernel    a lane per vertex: boundary / non-manifold / unused from its row, bad from its coordinates; two counters
 //   sm_pass_kernel<CLAMP>     a lane per vertex: the serial row walk, three f64 sums in ascending neighbour order, one division, the update,
 //                             the rounding to f32 and the f32 clamp around x0.  Ping-pong: it reads x_in and writes x_out.
 //   sm_normal_keys_kernel     a lane per face: three incidence keys, the corner's vertex or INT64_MAX
 //       torch.sort (stable) of the 3 T keys: plumbing
-//   sm_normals_kernel         a lane per vertex: a bisection finds its run, the f64 area vectors are summed in ascending slot order
+//   sm_normals_kernel         a lane per vertex: mesh_lower_bound finds its run, the f64 area vectors (mesh_area_vector) are summed in
+//                             ascending slot order
+//
+// From mesh_edit.h: MESH_NO_KEY, mesh_face_indices with mesh_face_distinct (a good face here: in range AND no repeated index), MeshCarve
+// (the workspace, sm_workspace), mesh_wave_count, mesh_run_tail, mesh_number_runs, mesh_lower_bound, mesh_area_vector, mesh_blocks.
 //
 // The f64 expressions are evaluated as written: the library is compiled with -ffp-contract=off (HIPCC_FLAGS in ngp_hip/lib.py), so
 // x + factor * (m - x) is a subtraction, a multiplication and an addition with a rounding each, never an fma; no fast-math flag is
@@ -21,64 +26,47 @@
 // No float atomics: every sum's order is fixed by the sorted keys, so two runs write the same bytes.  Integer atomics count (one per
 // wave); the adjacency is integer arithmetic only and depends on the set of faces alone.
 #include "ngp_device.h"
-#include "mesh_scan.h"
+#include "mesh_edit.h"
 
 namespace ngp {
 
-constexpr long long SM_NO_KEY = 0x7fffffffffffffffll;       // a bad face's slots: behind every real key (u V + w < V^2 < 2^62)
 constexpr int SM_MAX_MULTIPLICITY = 255;                    // multiplicity is uint8 and saturates here
 enum { SM_EDGES = 0, SM_BAD_FACES = 1, SM_BAD_VERTICES = 2, SM_BOUNDARY_VERTICES = 3, SM_COUNTS = 4 };
 enum { SM_BOUNDARY = 1, SM_NONMANIFOLD = 2, SM_UNUSED = 4, SM_BAD = 8 };
 
-__host__ __device__ __forceinline__ long long sm_align16(long long b) { return (b + 15) & ~15ll; }
 struct SmWorkspace {
     int32_t* run;             // [6 T]: the run number of every sorted slot
     uint8_t* heads;           // [6 T]: the first slot of a run
     int32_t* chunk;           // [chunks(6 T)]
+    long long bytes;
 };
-__host__ __forceinline__ SmWorkspace sm_workspace(void* base, long long n_keys) {
-    char* p = (char*)base;
+static SmWorkspace sm_workspace(void* base, long long n_keys) {
+    MeshCarve c{(char*)base, 0};
     SmWorkspace w;
-    w.run = (int32_t*)p;      p += sm_align16(4 * n_keys);
-    w.heads = (uint8_t*)p;    p += sm_align16(n_keys);
-    w.chunk = (int32_t*)p;
+    w.run = c.take<int32_t>(n_keys);
+    w.heads = c.take<uint8_t>(n_keys);
+    w.chunk = c.take<int32_t>(mesh_scan_chunks(n_keys));
+    w.bytes = c.used;
     return w;
 }
 
-// a good face: three indices inside [0, V), no two the same
-__device__ __forceinline__ bool sm_good_face(int a, int b, int c, int n_vertices) {
-    return (unsigned)a < (unsigned)n_vertices && (unsigned)b < (unsigned)n_vertices && (unsigned)c < (unsigned)n_vertices && a != b &&
-           b != c && c != a;
-}
-
-// counts[slot] += the number of lanes with `on`; every lane of the wave calls it
-__device__ __forceinline__ void sm_wave_count(int32_t* counts, int slot, bool on, int lane) {
-    const unsigned long long m = __ballot(on);
-    if (m && lane == __ffsll((long long)m) - 1) atomicAdd(&counts[slot], __popcll(m));
-}
-
+// six directed keys per face, u V + w < V^2 < 2^62: MESH_NO_KEY (a bad face's slots) sorts behind them
 __global__ void __launch_bounds__(256) sm_edge_keys_kernel(const int32_t* __restrict__ faces, int n_faces, int n_vertices,
                                                            long long* __restrict__ keys, int32_t* counts) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     bool bad = false;
     if (f < n_faces) {
-        const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-        bad = !sm_good_face(a, b, c, n_vertices);
-        const int u[3] = {a, b, c}, w[3] = {b, c, a};
+        int u[3];
+        mesh_face_indices(faces, f, u);
+        bad = !mesh_face_distinct(u, n_vertices);
+        const int w[3] = {u[1], u[2], u[0]};
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            keys[6 * f + 2 * k] = bad ? SM_NO_KEY : (long long)u[k] * n_vertices + w[k];
-            keys[6 * f + 2 * k + 1] = bad ? SM_NO_KEY : (long long)w[k] * n_vertices + u[k];
+            keys[6 * f + 2 * k] = bad ? MESH_NO_KEY : (long long)u[k] * n_vertices + w[k];
+            keys[6 * f + 2 * k + 1] = bad ? MESH_NO_KEY : (long long)w[k] * n_vertices + u[k];
         }
     }
-    sm_wave_count(counts, SM_BAD_FACES, bad, threadIdx.x & 63);
-}
-
-__global__ void __launch_bounds__(256) sm_heads_kernel(const long long* __restrict__ sorted_keys, long long n, uint8_t* __restrict__ heads) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const long long k = sorted_keys[i];
-    heads[i] = k != SM_NO_KEY && (i == 0 || sorted_keys[i - 1] != k) ? 1 : 0;
+    mesh_wave_count(&counts[SM_BAD_FACES], bad, threadIdx.x & 63);
 }
 
 __global__ void __launch_bounds__(256) sm_build_kernel(const long long* __restrict__ sorted_keys, const uint8_t* __restrict__ heads,
@@ -90,7 +78,7 @@ __global__ void __launch_bounds__(256) sm_build_kernel(const long long* __restri
     const int e = run[i];
     if ((unsigned long long)e >= (unsigned long long)n) return;             // neighbours and multiplicity hold n = 6 T slots
     int m = 1;
-    while (m < SM_MAX_MULTIPLICITY && i + m < n && sorted_keys[i + m] == k) ++m;
+    while (m < SM_MAX_MULTIPLICITY && !mesh_run_tail(sorted_keys, i + m - 1, n)) ++m;
     neighbours[e] = (int)(k % n_vertices);
     multiplicity[e] = (uint8_t)m;
 }
@@ -101,13 +89,8 @@ __global__ void __launch_bounds__(256) sm_rows_kernel(const long long* __restric
                                                       int32_t* __restrict__ row_start) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v > n_vertices) return;
-    const long long target = v * n_vertices;                               // <= V^2 < 2^62
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (sorted_keys[mid] < target) lo = mid + 1; else hi = mid;
-    }
-    row_start[v] = lo < n && sorted_keys[lo] != SM_NO_KEY ? run[lo] : counts[SM_EDGES];
+    const long long lo = mesh_lower_bound(sorted_keys, n, v * n_vertices);  // the target is <= V^2 < 2^62
+    row_start[v] = lo < n && sorted_keys[lo] != MESH_NO_KEY ? run[lo] : counts[SM_EDGES];
 }
 
 __global__ void __launch_bounds__(256) sm_vertex_flags_kernel(const float* __restrict__ vertices, int n_vertices,
@@ -131,8 +114,8 @@ __global__ void __launch_bounds__(256) sm_vertex_flags_kernel(const float* __res
         vertex_flags[v] = (uint8_t)flags;
     }
     const int lane = threadIdx.x & 63;
-    sm_wave_count(counts, SM_BAD_VERTICES, flags & SM_BAD, lane);
-    sm_wave_count(counts, SM_BOUNDARY_VERTICES, flags & SM_BOUNDARY, lane);
+    mesh_wave_count(&counts[SM_BAD_VERTICES], flags & SM_BAD, lane);
+    mesh_wave_count(&counts[SM_BOUNDARY_VERTICES], flags & SM_BOUNDARY, lane);
 }
 
 struct SmMove { float v[3]; };
@@ -190,11 +173,11 @@ __global__ void __launch_bounds__(256) sm_normal_keys_kernel(const int32_t* __re
                                                              long long* __restrict__ keys) {
     const long long f = (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= n_faces) return;
-    const int a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    const bool good = sm_good_face(a, b, c, n_vertices);
-    keys[3 * f] = good ? (long long)a : SM_NO_KEY;
-    keys[3 * f + 1] = good ? (long long)b : SM_NO_KEY;
-    keys[3 * f + 2] = good ? (long long)c : SM_NO_KEY;
+    int idx[3];
+    mesh_face_indices(faces, f, idx);
+    const bool good = mesh_face_distinct(idx, n_vertices);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) keys[3 * f + k] = good ? (long long)idx[k] : MESH_NO_KEY;
 }
 
 __global__ void __launch_bounds__(256) sm_normals_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces, int n_faces,
@@ -203,27 +186,17 @@ __global__ void __launch_bounds__(256) sm_normals_kernel(const float* __restrict
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v >= n_vertices) return;
     const long long n = 3ll * n_faces;
-    long long lo = 0, hi = n;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if (sorted_keys[mid] < v) lo = mid + 1; else hi = mid;
-    }
     double s[3] = {0.0, 0.0, 0.0};
-    for (long long i = lo; i < n && sorted_keys[i] == v; ++i) {                      // ascending slot: the sort is stable
+    for (long long i = mesh_lower_bound(sorted_keys, n, v); i < n && sorted_keys[i] == v; ++i) {      // ascending slot: the sort is stable
         const long long f = order[i] / 3;
         if (f < 0 || f >= n_faces) continue;
-        const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-        if (!sm_good_face(ia, ib, ic, n_vertices)) continue;
-        double a[3], u[3], w[3];
+        int idx[3];
+        mesh_face_indices(faces, f, idx);
+        if (!mesh_face_distinct(idx, n_vertices)) continue;
+        double a[3], b[3], c[3], nn[3];
+        mesh_area_vector(vertices, idx, a, b, c, nn);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            a[k] = (double)vertices[3ll * ia + k];
-            u[k] = (double)vertices[3ll * ib + k] - a[k];
-            w[k] = (double)vertices[3ll * ic + k] - a[k];
-        }
-        s[0] += 0.5 * (u[1] * w[2] - u[2] * w[1]);
-        s[1] += 0.5 * (u[2] * w[0] - u[0] * w[2]);
-        s[2] += 0.5 * (u[0] * w[1] - u[1] * w[0]);
+        for (int k = 0; k < 3; ++k) s[k] += 0.5 * nn[k];
     }
     const double len = sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
     const bool ok = len > 0.0 && len < INFINITY;                                      // false for a NaN too
@@ -235,15 +208,13 @@ __global__ void __launch_bounds__(256) sm_normals_kernel(const float* __restrict
 
 using namespace ngp;
 
-static unsigned sm_blocks(long long n) { return (unsigned)((n + 255) / 256); }
 static bool sm_sizes_ok(int n_faces, int n_vertices) { return n_vertices >= 1 && n_faces >= 1 && 6ll * n_faces <= 0x7fffffffll; }
 
 extern "C" {
 
 long long ngp_mesh_adjacency_bytes(int n_faces) {
     if (n_faces < 1 || 6ll * n_faces > 0x7fffffffll) return -1;
-    const long long n = 6ll * n_faces;
-    return sm_align16(4 * n) + sm_align16(n) + sm_align16(4 * mesh_scan_chunks(n));
+    return sm_workspace(nullptr, 6ll * n_faces).bytes;
 }
 
 int ngp_mesh_adjacency_keys(const int32_t* faces, int n_faces, int n_vertices, int64_t* keys, int32_t* counts, void* stream) {
@@ -251,7 +222,7 @@ int ngp_mesh_adjacency_keys(const int32_t* faces, int n_faces, int n_vertices, i
     hipStream_t s = (hipStream_t)stream;
     const hipError_t e = hipMemsetAsync(counts, 0, SM_COUNTS * sizeof(int32_t), s);
     if (e != hipSuccess) return -(int)e;
-    hipLaunchKernelGGL(sm_edge_keys_kernel, dim3(sm_blocks(n_faces)), dim3(256), 0, s, faces, n_faces, n_vertices, (long long*)keys, counts);
+    hipLaunchKernelGGL(sm_edge_keys_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, s, faces, n_faces, n_vertices, (long long*)keys, counts);
     NGP_LAUNCH_CHECK();
     return 0;
 }
@@ -266,12 +237,11 @@ int ngp_mesh_adjacency_build(const float* vertices, int n_faces, int n_vertices,
     const SmWorkspace w = sm_workspace(workspace, n);
     hipStream_t s = (hipStream_t)stream;
     const long long* keys = (const long long*)sorted_keys;
-    hipLaunchKernelGGL(sm_heads_kernel, dim3(sm_blocks(n)), dim3(256), 0, s, keys, n, w.heads);
-    mesh_scan<true>(w.heads, 1, n, w.chunk, w.run, counts + SM_EDGES, s);
-    hipLaunchKernelGGL(sm_build_kernel, dim3(sm_blocks(n)), dim3(256), 0, s, keys, w.heads, w.run, n, n_vertices, neighbours, multiplicity);
-    hipLaunchKernelGGL(sm_rows_kernel, dim3(sm_blocks((long long)n_vertices + 1)), dim3(256), 0, s, keys, w.run, n, n_vertices, counts,
+    mesh_number_runs(keys, n, w.heads, w.chunk, w.run, counts + SM_EDGES, s);
+    hipLaunchKernelGGL(sm_build_kernel, dim3(mesh_blocks(n, 256)), dim3(256), 0, s, keys, w.heads, w.run, n, n_vertices, neighbours, multiplicity);
+    hipLaunchKernelGGL(sm_rows_kernel, dim3(mesh_blocks((long long)n_vertices + 1, 256)), dim3(256), 0, s, keys, w.run, n, n_vertices, counts,
                        row_start);
-    hipLaunchKernelGGL(sm_vertex_flags_kernel, dim3(sm_blocks(n_vertices)), dim3(256), 0, s, vertices, n_vertices, row_start, multiplicity,
+    hipLaunchKernelGGL(sm_vertex_flags_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, vertices, n_vertices, row_start, multiplicity,
                        n, vertex_flags, counts);
     NGP_LAUNCH_CHECK();
     return 0;
@@ -298,10 +268,10 @@ int ngp_mesh_smooth(float* x_a, float* x_b, const float* x0, const int32_t* row_
     for (long long p = 0; p < (long long)n_iterations * per_iteration; ++p) {
         const double factor = per_iteration == 2 && (p & 1) ? mu : lambda;
         if (clamp)
-            hipLaunchKernelGGL(sm_pass_kernel<true>, dim3(sm_blocks(n_vertices)), dim3(256), 0, s, in, x0, row_start, neighbours, multiplicity,
+            hipLaunchKernelGGL(sm_pass_kernel<true>, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, in, x0, row_start, neighbours, multiplicity,
                                vertex_flags, fixed, n_vertices, n_slots, factor, boundary_mode, mm, out);
         else
-            hipLaunchKernelGGL(sm_pass_kernel<false>, dim3(sm_blocks(n_vertices)), dim3(256), 0, s, in, x0, row_start, neighbours, multiplicity,
+            hipLaunchKernelGGL(sm_pass_kernel<false>, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, s, in, x0, row_start, neighbours, multiplicity,
                                vertex_flags, fixed, n_vertices, n_slots, factor, boundary_mode, mm, out);
         float* t = in; in = out; out = t;
     }
@@ -311,7 +281,7 @@ int ngp_mesh_smooth(float* x_a, float* x_b, const float* x0, const int32_t* row_
 
 int ngp_mesh_vertex_normals_keys(const int32_t* faces, int n_faces, int n_vertices, int64_t* keys, void* stream) {
     if (!faces || !keys || !sm_sizes_ok(n_faces, n_vertices)) return -1;
-    hipLaunchKernelGGL(sm_normal_keys_kernel, dim3(sm_blocks(n_faces)), dim3(256), 0, (hipStream_t)stream, faces, n_faces, n_vertices,
+    hipLaunchKernelGGL(sm_normal_keys_kernel, dim3(mesh_blocks(n_faces, 256)), dim3(256), 0, (hipStream_t)stream, faces, n_faces, n_vertices,
                        (long long*)keys);
     NGP_LAUNCH_CHECK();
     return 0;
@@ -320,7 +290,7 @@ int ngp_mesh_vertex_normals_keys(const int32_t* faces, int n_faces, int n_vertic
 int ngp_mesh_vertex_normals(const float* vertices, const int32_t* faces, int n_faces, int n_vertices, const int64_t* sorted_keys,
                             const int64_t* order, float* normals, void* stream) {
     if (!vertices || !faces || !sorted_keys || !order || !normals || !sm_sizes_ok(n_faces, n_vertices)) return -1;
-    hipLaunchKernelGGL(sm_normals_kernel, dim3(sm_blocks(n_vertices)), dim3(256), 0, (hipStream_t)stream, vertices, faces, n_faces,
+    hipLaunchKernelGGL(sm_normals_kernel, dim3(mesh_blocks(n_vertices, 256)), dim3(256), 0, (hipStream_t)stream, vertices, faces, n_faces,
                        n_vertices, (const long long*)sorted_keys, (const long long*)order, normals);
     NGP_LAUNCH_CHECK();
     return 0;

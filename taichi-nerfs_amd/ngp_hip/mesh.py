@@ -166,9 +166,7 @@ def components(mesh, strict=True):
     (mesh_sdf.weld_vertices).  A face with an index outside [0, V) joins nothing; strict=True raises ValueError when there is one,
     strict=False labels it -1 and counts it."""
     vertices, faces = mesh[0], mesh[1]
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
-    ops._dev(vertices, torch.float32, "vertices")
+    ops._mesh_arrays(vertices)
     vc, fc, counts, rounds = ops.mesh_components_label(faces, vertices.shape[0])
     n, bad, unused = counts.tolist()                                     # the labelling's host read besides the round flags
     if bad and strict:
@@ -312,10 +310,7 @@ def simplify_mesh(mesh, cell=None, resolution=None, target_faces=None, bounds=No
     if sum(x is not None for x in (cell, resolution, target_faces)) != 1:
         raise ValueError("give exactly one of cell, resolution and target_faces")
     vertices, faces = mesh[0], mesh[1]
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
-    ops._dev(vertices, torch.float32, "vertices")
-    n_faces, n_vertices = ops._mesh_faces(faces, vertices.shape[0])
+    n_faces, n_vertices = ops._mesh_arrays(vertices, faces)
     if not float(regularization) > 0.0:
         raise ValueError("regularization must be positive (inf: the cluster mean), got %r" % (regularization,))
     dev = vertices.device

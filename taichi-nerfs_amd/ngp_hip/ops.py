@@ -1013,6 +1013,21 @@ def _mesh_faces(faces, n_vertices):
     return int(faces.shape[0]), n_vertices
 
 
+def _mesh_arrays(vertices, faces=None):
+    """The checks every mesh entry makes of its vertices f32 [V,3] and, where it takes them, its faces -> (T, V); T = 0 without faces."""
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
+    _dev(vertices, torch.float32, "vertices")
+    return _mesh_faces(faces, vertices.shape[0]) if faces is not None else (0, int(vertices.shape[0]))
+
+
+def _mesh_mask(mask, name):
+    """A per-component or per-vertex mask (uint8 / bool, on the device) as the kernels read it."""
+    if not mask.is_cuda:
+        raise RuntimeError("%s must live on the GPU: libngp_hip has no CPU path (got device %s)" % (name, mask.device))
+    return mask.to(torch.uint8).contiguous()
+
+
 def _mesh_components_workspace(n_faces, n_vertices, device):
     return torch.empty(_lib().ngp_mesh_components_bytes(n_faces, n_vertices), device=device, dtype=torch.uint8)
 
@@ -1079,11 +1094,8 @@ def mesh_components_table(faces, n_vertices, vertex_component, face_component, n
 def mesh_components_measure(vertices, faces, face_component, face_counts, n_bad):
     """Area f64 [C], signed volume f64 [C] and the box lo, hi f32 [C,3] of every component, summed in an order the input fixes.
     face_counts int32 [C]: the table's faces column; n_bad: the number of bad faces (they sort first)."""
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
-    _dev(vertices, torch.float32, "vertices"); _dev(face_counts, torch.int32, "face_counts")
-    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
-    _dev(face_component, torch.int32, "face_component")
+    n_faces, n_vertices = _mesh_arrays(vertices, faces)
+    _dev(face_counts, torch.int32, "face_counts"); _dev(face_component, torch.int32, "face_component")
     if tuple(face_component.shape) != (n_faces,):
         raise ValueError("face_component must be [T]")
     dev, n_components = faces.device, int(face_counts.shape[0])
@@ -1108,17 +1120,13 @@ def mesh_select(vertices, normals, faces, vertex_component, face_component, keep
     """The sub-mesh of the components keep (uint8 / bool [C], on the device) marks -> (vertices, normals or None, faces, vertex_map int32
     [V], face_map int32 [T]): kept rows in their original relative order, faces re-indexed, the maps -1 for what is dropped.  One host
     read (the two sizes); an empty selection launches no emit."""
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
-    _dev(vertices, torch.float32, "vertices")
+    _mesh_arrays(vertices)
     n_faces, n_vertices = _mesh_labels(faces, vertices.shape[0], vertex_component, face_component)
     if normals is not None:
         _dev(normals, torch.float32, "normals")
         if tuple(normals.shape) != tuple(vertices.shape):
             raise ValueError("normals must be [V,3] like the vertices")
-    if not keep.is_cuda:
-        raise RuntimeError("keep must live on the GPU: libngp_hip has no CPU path (got device %s)" % keep.device)
-    keep = keep.to(torch.uint8).contiguous()
+    keep = _mesh_mask(keep, "keep")
     dev, n_components = faces.device, int(keep.shape[0])
     vertex_map = torch.full((n_vertices,), -1, device=dev, dtype=torch.int32)
     face_map = torch.full((n_faces,), -1, device=dev, dtype=torch.int32)
@@ -1163,10 +1171,7 @@ def mesh_simplify_count(vertices, faces, lo, h, n):
     the cluster numbering, surviving faces and the two maps -> a SimpleNamespace with vertex_map int32 [V], face_map int32 [T], counts
     int32 [5] (MESH_SIMPLIFY_COUNTS) ON THE DEVICE, and what mesh_simplify_emit needs.  No quadric is formed, nothing is read back.
     V >= 1; T = 0 is allowed."""
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
-    _dev(vertices, torch.float32, "vertices")
-    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
+    n_faces, n_vertices = _mesh_arrays(vertices, faces)
     if n_vertices < 1:
         raise ValueError("mesh_simplify_count needs at least one vertex")
     grid = _mesh_simplify_grid(lo, h, n)
@@ -1194,8 +1199,7 @@ def mesh_simplify_emit(vertices, faces, state, n_clusters, n_out_vertices, n_out
     regularization = float(regularization)
     if not regularization > 0.0:
         raise ValueError("regularization must be positive (inf: the cluster mean), got %r" % (regularization,))
-    _dev(vertices, torch.float32, "vertices")
-    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
+    n_faces, n_vertices = _mesh_arrays(vertices, faces)
     dev = vertices.device
     out_v = torch.empty(n_out_vertices, 3, device=dev, dtype=torch.float32)
     out_n = torch.empty(n_out_vertices, 3, device=dev, dtype=torch.float32) if normals else None
@@ -1225,10 +1229,7 @@ MESH_FLAG_BOUNDARY, MESH_FLAG_NONMANIFOLD, MESH_FLAG_UNUSED, MESH_FLAG_BAD = 1, 
 
 
 def _mesh_smooth_sizes(vertices, faces):
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
-    _dev(vertices, torch.float32, "vertices")
-    n_faces, n_vertices = _mesh_faces(faces, vertices.shape[0])
+    n_faces, n_vertices = _mesh_arrays(vertices, faces)
     if 6 * n_faces >= 2**31:
         raise ValueError("the mesh has %d faces; the adjacency's key list holds at most 2^31 - 1 directed edges" % n_faces)
     return n_faces, n_vertices
@@ -1266,10 +1267,7 @@ def mesh_smooth(vertices, row_start, neighbours, multiplicity, vertex_flags, ite
     """`iterations` Taubin iterations (a lambda pass, then a mu pass; mu = 0: lambda passes only) over the CSR of mesh_adjacency ->
     new positions f32 [V,3]; `vertices` is not written.  max_move: None or three floats >= 0 (inf: no bound on that axis), the bound
     on the displacement from `vertices`.  fixed: uint8 / bool [V] on the device or None.  No host read."""
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError("vertices must be [V,3], got %s" % (tuple(vertices.shape),))
-    _dev(vertices, torch.float32, "vertices")
-    n_vertices = int(vertices.shape[0])
+    n_vertices = _mesh_arrays(vertices)[1]
     _dev(row_start, torch.int32, "row_start"); _dev(neighbours, torch.int32, "neighbours")
     _dev(multiplicity, torch.uint8, "multiplicity"); _dev(vertex_flags, torch.uint8, "vertex_flags")
     if tuple(row_start.shape) != (n_vertices + 1,) or tuple(vertex_flags.shape) != (n_vertices,) or neighbours.dim() != 1 \
@@ -1284,11 +1282,9 @@ def mesh_smooth(vertices, row_start, neighbours, multiplicity, vertex_flags, ite
     if not (move >= 0).all():
         raise ValueError("max_move must be >= 0 (inf: no bound), got %r" % (max_move,))
     if fixed is not None:
-        if not fixed.is_cuda:
-            raise RuntimeError("fixed must live on the GPU: libngp_hip has no CPU path (got device %s)" % fixed.device)
+        fixed = _mesh_mask(fixed, "fixed")
         if tuple(fixed.shape) != (n_vertices,):
             raise ValueError("fixed must be [V]")
-        fixed = fixed.to(torch.uint8).contiguous()
     x_a = vertices.clone()
     passes = iterations * (1 if mu == 0.0 else 2)
     if n_vertices == 0 or passes == 0 or neighbours.shape[0] == 0:          # no edge: every vertex is unused, nothing moves

@@ -61,6 +61,23 @@ def test_disjoint_triangles(n):
     assert cc.n == n and cc.rounds == (2 if n else 0)
 
 
+# ---- the two per-wave counters (bad faces in cc_mark_kernel, unused vertices in cc_assign_vertices_kernel): whole waves, a lone lane, a
+# wave with its tail past the end, several blocks; all, half and a seventh of the faces bad; V / 3 unused vertices behind the used ones
+@pytest.mark.parametrize("every", [1, 2, 7])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 513])
+def test_bad_faces_and_unused_vertices_are_counted_per_wave(n, every):
+    v, f = R.disjoint_triangles(n, seed=n)
+    v = np.concatenate([v, np.full((len(v) // 3, 3), 0.25, np.float32)])
+    f = f.copy()
+    bad = np.arange(0, n, every)
+    f[bad[0::2], 1] = len(v)                                                   # the first index past the end
+    f[bad[1::2], 2] = -1
+    lab = R.label(f, len(v))
+    assert lab["bad_faces"] == len(bad) and lab["unused_vertices"] == n + 3 * len(bad) and lab["n"] == n - len(bad)
+    cc = _check(v, f, strict=False, ref=(lab, R.table(v, f, lab)), what="bad every %d" % every)
+    assert cc.rounds == (2 if len(bad) < n else 1)             # a pass that joins every good face, a pass that finds nothing to join
+
+
 def test_no_vertices_and_no_faces():
     empty_f = np.zeros((0, 3), np.int32)
     cc = _check(np.zeros((0, 3), np.float32), empty_f)
