@@ -18,7 +18,15 @@ connected components on the device) and print its report and the topology before
 --smooth_max_move CELLS (default 0.5) spacings of the extraction grid.  It prints one JSON line: the seconds, the boundary vertices, the
 mean and the largest displacement in cells; with --sdf, where the true surface is known, also the mean distance of the vertices from
 the sphere (in cells) and the mean angle between the face normals and the sphere's (in degrees), before and after.  The normals of a
-smoothed mesh are ngp_hip.vertex_normals of the new positions."""
+smoothed mesh are ngp_hip.vertex_normals of the new positions.
+--colors field | images (off by default; --train_steps or --ckpt) colours the final mesh, after every other step: `field` asks the model
+for its colour looking down the normal, --field_offset CELLS grid spacings along it from the vertex (default -2, inside: the level set of
+the occupancy threshold lies in the fuzzy rim of the density, where the colour is barely trained; DESIGN.md has the PSNR per offset),
+`images` renders --views N posed views of the procedural scene and bakes them
+onto the vertices with an occlusion test against the mesh itself.  The file then carries the colours (uchar red green blue in a .ply,
+`v x y z r g b` in an .obj), and one JSON line reports the seconds, how many vertices were baked, filled from their neighbours or left at
+the default, and the PSNR of the coloured mesh rendered from held-out poses (ngp_hip.render_mesh(colors=)) against the synthetic views
+there, over the pixels where both are hit."""
 import argparse
 import json
 import math
@@ -99,6 +107,52 @@ def train_procedural_model(steps, dev, wh=100, n_views=40, batch=8192):
     return model, thr
 
 
+def color_mesh(how, msh, model, dev, n_views=40, wh=200, n_held_out=4, field_offset=0.0):
+    """Vertex colours for a mesh of the procedural scene -> (colors [V,3], report).  how = "images": n_views posed views of the scene
+    (ngp_hip.synthetic, the cameras of the training set's kind) baked with ngp_hip.bake_image_colors; "field": the model's colour at the
+    vertices moved by field_offset (world units) along the normal, looking down the normal (ngp_hip.bake_field_colors, the evaluation
+    loops' autocast).  The coloured mesh is then rendered
+    from n_held_out other poses with render_mesh(colors=) and compared with the synthetic views there: the PSNR over the pixels where
+    both the mesh and the scene are hit."""
+    from ngp_hip import MeshSDF, bake_field_colors, bake_image_colors, render_mesh
+    from ngp_hip.synthetic import procedural_render_gt
+    focal = 1111.1 * wh / 800
+    ys, xs = torch.meshgrid(torch.arange(wh, device=dev), torch.arange(wh, device=dev), indexing="ij")
+    dirs = torch.stack([(xs - wh / 2 + 0.5) / focal, (ys - wh / 2 + 0.5) / focal, torch.ones_like(xs, dtype=torch.float32)], -1).reshape(-1, 3)
+    K = torch.tensor([[focal, 0, wh / 2], [0, focal, wh / 2], [0, 0, 1]], device=dev)
+    views = lambda poses: torch.stack([procedural_render_gt(p[:, 3].expand_as(dirs), dirs @ p[:, :3].T) for p in poses]).view(-1, wh, wh, 3)
+    report = {"colors": how, "image_wh": wh}
+    target = MeshSDF.from_mesh(msh, signed=False)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    if how == "images":
+        poses = _cameras(n_views, 1.39, 41, dev)
+        images = views(poses).contiguous()
+        torch.cuda.synchronize()
+        t1 = time.time()
+        vc = bake_image_colors(msh, images, K, poses, target=target)
+        colors = vc.colors
+        torch.cuda.synchronize()
+        report.update(views=n_views, render_seconds=t1 - t0, bake_seconds=time.time() - t1, baked=int((vc.filled == 0).sum()),
+                      filled=int(((vc.filled > 0) & (vc.filled < 255)).sum()), default=int((vc.filled == 255).sum()),
+                      mean_views=float(vc.views.float().mean()))
+    else:
+        with torch.autocast("cuda", dtype=torch.float16):
+            colors = bake_field_colors(model, msh, offset=field_offset)
+        torch.cuda.synchronize()
+        report.update(bake_seconds=time.time() - t0, field_offset=field_offset)
+    held_out = _cameras(n_held_out, 1.39, 977, dev)
+    truth = views(held_out)
+    se, count = 0.0, 0
+    for pose, gt in zip(held_out, truth):
+        out = render_mesh(target, K, pose, (wh, wh), colors=colors)
+        both = out["mask"] & (gt < 0.999).any(-1)                            # the scene's background is white, its boxes never are
+        se += float(((out["rgb"] - gt)[both] ** 2).sum())
+        count += 3 * int(both.sum())
+    report.update(held_out_views=n_held_out, pixels_compared=count // 3, psnr=-10.0 * math.log10(se / count) if count and se > 0 else None)
+    return colors, report
+
+
 def sphere_errors(msh, cell):
     """(mean | |v - 0.5| - 0.3 | over the vertices in cells, mean angle in degrees between the face normals and the sphere's normal at the
     face centroids) of a mesh of the --sdf sphere."""
@@ -136,6 +190,12 @@ def main(argv=None):
                     help="smooth the mesh before writing it: N Taubin iterations with the boundary fixed (ngp_hip.smooth_mesh); 0: off")
     ap.add_argument("--smooth_max_move", type=float, default=0.5, metavar="CELLS",
                     help="smoothing moves no coordinate farther than this many spacings of the extraction grid")
+    ap.add_argument("--colors", default="none", choices=["none", "field", "images"],
+                    help="vertex colours for the final mesh of the procedural scene: the model's colour at the vertices "
+                         "(ngp_hip.bake_field_colors) or baked from --views posed views of the scene (ngp_hip.bake_image_colors)")
+    ap.add_argument("--views", type=int, default=40, metavar="N", help="--colors images: the number of views to bake from")
+    ap.add_argument("--field_offset", type=float, default=-2.0, metavar="CELLS",
+                    help="--colors field: ask the model this many spacings of the extraction grid along the normal (negative: inside)")
     ap.add_argument("--scale", type=float, default=0.5)
     # the --sdf fit (fit_sdf_eikonal.py's options); --max_res also sizes the NGP of --ckpt
     ap.add_argument("--steps", type=int, default=500)
@@ -231,8 +291,19 @@ def main(argv=None):
         info.update(simplify=dict(vertices=int(msh.vertices.shape[0]), faces=int(msh.faces.shape[0]), before=before, cell=list(res.h),
                                   grid=list(res.grid), clusters=res.n_clusters, seconds=time.time() - t_simplify))
         print("simplify_mesh:", json.dumps(info["simplify"]))
+    colors = None
+    if args.colors != "none":                                                # off by default; last: colours belong to the final vertices
+        if args.sdf:
+            raise SystemExit("--colors needs a model of the procedural scene (--train_steps or --ckpt)")
+        if args.views < 1:
+            raise SystemExit("--views must be positive")
+        if msh.faces.shape[0]:
+            colors, report = color_mesh(args.colors, msh, model, dev, n_views=args.views, field_offset=args.field_offset * min(cell))
+            info.update(colors=report)
+            print("colors:", json.dumps(report))
     t_write = time.time()
-    (mesh.write_ply if args.out.endswith(".ply") else mesh.write_obj)(args.out, msh)
+    write = mesh.write_ply if args.out.endswith(".ply") else mesh.write_obj
+    write(args.out, msh) if colors is None else write(args.out, msh, colors=colors)
     t3 = time.time()
     info.update(mesh.topology(msh))
     info.update(resolution=args.resolution, normals=args.normals, out=args.out, prepare_seconds=t1 - t0, extract_seconds=t2 - t1,

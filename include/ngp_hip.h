@@ -936,6 +936,49 @@ int ngp_mesh_vertex_normals_keys(const int32_t* faces, int n_faces, int n_vertic
 int ngp_mesh_vertex_normals(const float* vertices, const int32_t* faces, int n_faces, int n_vertices, const int64_t* sorted_keys,
                             const int64_t* order, float* normals /*[V,3]*/, void* stream);
 
+/* ---- vertex colours from posed images (csrc/mesh_color.hip; DESIGN.md section 3, "Vertex colours").  vertices f32 [V,3], normals f32
+ * [V,3] (unit), K f32 [3,3] (k_per_camera = 0) or [N,3,3] (1), c2w f32 [N,3,4] = (right, down, front | position) as ngp_get_rays reads it,
+ * images f32 [N,H,W,C], C >= 3 (the first three channels are used), 1 <= V, 1 <= N, V N <= 2^31 - 1.  N is the number of cameras of ONE
+ * CHUNK: the caller cuts the cameras into chunks, in ascending order, and passes each chunk's slices; accum, views and best_cos carry
+ * across the chunks, and because every vertex meets its cameras in ascending index the result has the same bits for every chunk size.
+ * PAIR j V + v is camera j of the chunk and vertex v.  In f32, every operation rounded once, dots as (x + y) + z:
+ *     d = c - v;  nd = n . d;  two_sided and nd < 0: n = -n, nd = -nd;  cos = nd / sqrt(d . d)
+ *     q = v - c;  p = (right . q, down . q, front . q)
+ *     u = fx p.x / p.z + cx;  w = fy p.y / p.z + cy;  a = u - 0.5;  b = w - 0.5       the centre of pixel (i, j) is (i + 0.5, j + 0.5)
+ *     ACCEPTED iff cos > cos_min and p.z > near and 0 <= a <= W - 1 and 0 <= b <= H - 1 and v and n are finite (a NaN fails)
+ *     accepted: rays_o = v + eps n, rays_d = c - rays_o, sample = (a, b), cosv = cos, weight = cos cos
+ *     rejected: rays_o = rays_d = 0 (ngp_mesh_raycast writes a miss for a zero direction without a walk), sample = cosv = weight = 0
+ * eps: ONE f32 IN DEVICE MEMORY (no host read behind a default that depends on the mesh).  cos_min >= 0 and near >= 0.
+ * OCCLUSION is ngp_mesh_raycast on rays_o, rays_d of the chunk with NGP_RAYCAST_ANY_HIT and t in [0, 1], called by the caller: t [V N].
+ * ACCUMULATE (a lane per vertex, cameras j = 0 .. N - 1 in that order).  A pair COUNTS iff weight > 0 and t = +inf.  For one that counts:
+ *     x0 = floor(a), y0 = floor(b), x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1), fx = a - x0, fy = b - y0 (f32, exact), then in f64
+ *     rgb_k = (1 - fy) ((1 - fx) I[y0,x0,k] + fx I[y0,x1,k]) + fy ((1 - fx) I[y1,x0,k] + fx I[y1,x1,k])
+ *     NGP_MESH_COLOR_BLEND: accum[v] += (w rgb_0, w rgb_1, w rgb_2, w), views[v] += 1
+ *     NGP_MESH_COLOR_BEST : only if cos > best_cos[v], strictly (of equal cos the lowest camera stays): accum[v] = (w rgb, w),
+ *                           views[v] = 1, best_cos[v] = cos
+ *   accum f64 [V,4], views int32 [V] and best_cos f32 [V] (BEST only, else it may be NULL) start as zeroes.
+ * FINISH: views > 0: colors = (float)(accum_k / accum_3), weight = (float)accum_3, filled = 0; else colors = weight = 0, filled = 255.
+ * FILL, one Jacobi round over the CSR of ngp_mesh_adjacency_build: a vertex with filled_in = 255 and at least one neighbour with
+ * filled_in != 255 takes the f64 mean of those neighbours' colours, summed in ascending neighbour order and rounded once, and
+ * filled_out = round (1 .. 254); every other vertex copies filled_in.  colors is updated in place: a round writes only vertices that were
+ * 255 in filled_in and reads only vertices that were not.  filled_in and filled_out must be two arrays.
+ * No atomics: the same input gives the same bytes.  All return -1 without a launch for a null required pointer, a size outside the
+ * limits, an unknown mode, a cos_min or near that is negative or NaN, or a round outside 1 .. 254. */
+#define NGP_MESH_COLOR_BLEND 0
+#define NGP_MESH_COLOR_BEST 1
+int ngp_mesh_color_project(const float* vertices, const float* normals, int n_vertices, const float* K, int k_per_camera,
+                           const float* c2w, int n_cameras, int width, int height, const float* eps /* device [1] */, float cos_min,
+                           float near, int two_sided, float* rays_o /*[V N,3]*/, float* rays_d /*[V N,3]*/, float* sample /*[V N,2]*/,
+                           float* weight /*[V N]*/, float* cosv /*[V N]*/, void* stream);
+int ngp_mesh_color_accumulate(const float* images, int n_cameras, int height, int width, int channels, int n_vertices,
+                              const float* sample, const float* weight, const float* cosv, const float* t, int mode,
+                              double* accum /*[V,4]*/, int32_t* views /*[V]*/, float* best_cos /*[V], may be NULL for BLEND*/,
+                              void* stream);
+int ngp_mesh_color_finish(const double* accum, const int32_t* views, int n_vertices, float* colors /*[V,3]*/, float* weight /*[V]*/,
+                          uint8_t* filled /*[V]*/, void* stream);
+int ngp_mesh_color_fill(float* colors, const uint8_t* filled_in, uint8_t* filled_out, const int32_t* row_start,
+                        const int32_t* neighbours, int n_vertices, long long n_slots, int round, void* stream);
+
 /* ---- surface rendering: the compositor of a-7 driven by a signed distance (NeuS opacity) (csrc/surface.hip) ---------------------------
  * Per sample j of a ray: f_j = sdf, c_j = cosv = dir . grad f (formed by the caller), delta_j, t_j, rgb_j [3] and, unless aux is NULL,
  * aux_j [3] (e.g. the unit normal).  Per launch: s = inv_s[0] (DEVICE memory, one float: no host read), r = cos_anneal in [0, 1],

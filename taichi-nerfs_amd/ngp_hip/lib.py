@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(CSRC, "libngp_hip.so")
 SOURCES = ["march.hip", "hash_grid.hip", "hash_bwd_lds.hip", "composite.hip", "sh_grid.hip", "mlp.hip", "optim.hip", "distortion.hip", "occupancy.hip", "rays.hip",
            "render.hip", "exchange.hip", "triplane.hip", "voxel_grid.hip", "deploy.hip", "hash_grad_input.hip", "hash_grad_input2.hip", "mesh.hip",
            "ray_grad.hip", "surface.hip", "resample.hip", "sdf_trace.hip", "mesh_sdf.hip", "mesh_raycast.hip", "mesh_winding.hip",
-           "mesh_components.hip", "mesh_simplify.hip", "mesh_smooth.hip"]
+           "mesh_components.hip", "mesh_simplify.hip", "mesh_smooth.hip", "mesh_color.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 FLAGS_STAMP = LIB_PATH + ".flags"      # the flags the in-tree .so was built with: a flag change rebuilds
 ABI_HEADERS = [os.path.join(INCLUDE, "ngp_hip.h"), os.path.join(INCLUDE, "ngp_hip_experimental.h")]

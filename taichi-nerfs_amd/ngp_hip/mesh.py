@@ -440,26 +440,50 @@ def _host(mesh):
     return v, f, n
 
 
-def write_ply(path, mesh):
-    """Binary little-endian PLY: float x y z (+ nx ny nz when the mesh has normals) per vertex, uchar 3 + three int32 per face."""
+def _host_colors(colors, n_vertices):
+    c = np.ascontiguousarray(torch.as_tensor(colors).detach().cpu().numpy(), dtype="<f4")
+    if c.shape != (n_vertices, 3):
+        raise ValueError("colors must be [V,3] like the vertices, got %s" % (c.shape,))
+    return c
+
+
+def color_bytes(colors):
+    """float colours -> uint8 as the PLY stores them: round(clamp(c, 0, 1) * 255), halves to even; a NaN becomes 0."""
+    c = np.nan_to_num(np.asarray(colors, np.float32), nan=0.0)
+    return np.rint(np.clip(c, 0.0, 1.0) * np.float32(255.0)).astype(np.uint8)
+
+
+def write_ply(path, mesh, colors=None):
+    """Binary little-endian PLY: float x y z (+ nx ny nz when the mesh has normals) per vertex, uchar 3 + three int32 per face.
+    colors [V,3] float: also uchar red green blue per vertex, after the normals, as color_bytes rounds them."""
     v, f, n = _host(mesh)
     props = ["x", "y", "z"] + (["nx", "ny", "nz"] if n is not None else [])
     header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v)] + ["property float %s" % p for p in props] \
+        + (["property uchar %s" % p for p in ("red", "green", "blue")] if colors is not None else []) \
         + ["element face %d" % len(f), "property list uchar int vertex_indices", "end_header"]
     rows = np.empty(len(f), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     rows["n"], rows["idx"] = 3, f
+    xyz = (v if n is None else np.concatenate([v, n], 1)).astype("<f4")
+    if colors is not None:
+        table = np.empty(len(v), dtype=[("f", "<f4", (xyz.shape[1],)), ("c", "u1", (3,))])
+        table["f"], table["c"] = xyz, color_bytes(_host_colors(colors, len(v)))
+        xyz = table
     with open(path, "wb") as fh:
         fh.write(("\n".join(header) + "\n").encode("ascii"))
-        fh.write((v if n is None else np.concatenate([v, n], 1)).astype("<f4").tobytes())
+        fh.write(xyz.tobytes())
         fh.write(rows.tobytes())
 
 
-def write_obj(path, mesh):
-    """Wavefront OBJ: v (and vn) lines with nine significant digits (an f32 survives the round trip), 1-based f lines."""
+def write_obj(path, mesh, colors=None):
+    """Wavefront OBJ: v (and vn) lines with nine significant digits (an f32 survives the round trip), 1-based f lines.  colors [V,3]
+    float: the v lines read `v x y z r g b`, the colours unclamped and with nine digits too."""
     v, f, n = _host(mesh)
     with open(path, "w") as fh:
         fh.write("# %d vertices, %d faces\n" % (len(v), len(f)))
-        fh.writelines("v %.9g %.9g %.9g\n" % tuple(r) for r in v.tolist())
+        if colors is not None:
+            fh.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % tuple(r) for r in np.concatenate([v, _host_colors(colors, len(v))], 1).tolist())
+        else:
+            fh.writelines("v %.9g %.9g %.9g\n" % tuple(r) for r in v.tolist())
         if n is not None:
             fh.writelines("vn %.9g %.9g %.9g\n" % tuple(r) for r in n.tolist())
             fh.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist())
@@ -467,9 +491,10 @@ def write_obj(path, mesh):
             fh.writelines("f %d %d %d\n" % tuple(r) for r in (f + 1).tolist())
 
 
-def read_ply(path):
+def read_ply(path, return_colors=False):
     """Reads exactly what write_ply writes -> Mesh of CPU tensors, bit for bit.  Any other header (ascii, big endian, other properties
-    or elements, polygons that are not triangles) raises ValueError."""
+    or elements, polygons that are not triangles) raises ValueError.  return_colors=True: -> (Mesh, colors), colors f32 [V,3] = the
+    file's uchar red green blue / 255, or None for a file without them; a file with colours raises without it."""
     with open(path, "rb") as fh:
         data = fh.read()
     end = data.find(b"end_header\n")
@@ -478,36 +503,49 @@ def read_ply(path):
     lines = data[:end].decode("ascii", "replace").split("\n")[:-1]
     body = data[end + len(b"end_header\n"):]
     xyz, nrm = ["property float %s" % p for p in "xyz"], ["property float %s" % p for p in ("nx", "ny", "nz")]
+    rgb = ["property uchar %s" % p for p in ("red", "green", "blue")]
     if len(lines) < 8 or lines[:2] != ["ply", "format binary_little_endian 1.0"] or not lines[2].startswith("element vertex ") \
             or lines[3:6] != xyz or lines[-1] != "property list uchar int vertex_indices" or not lines[-2].startswith("element face ") \
-            or lines[6:-2] not in ([], nrm):
+            or lines[6:-2] not in ([[], nrm, rgb, nrm + rgb] if return_colors else [[], nrm]):
         raise ValueError("%s: not the PLY layout write_ply produces (binary little endian, float x y z [nx ny nz], uchar/int faces)" % path)
     try:
         n_v, n_f = int(lines[2].split()[2]), int(lines[-2].split()[2])
     except ValueError:
         raise ValueError("%s: malformed element counts" % path) from None
-    cols = 3 + len(lines[6:-2])
-    if n_v < 0 or n_f < 0 or len(body) != 4 * cols * n_v + 13 * n_f:
-        raise ValueError("%s: the body holds %d bytes, the header announces %d" % (path, len(body), 4 * cols * n_v + 13 * n_f))
-    v = np.frombuffer(body, "<f4", cols * n_v).reshape(n_v, cols)
-    rows = np.frombuffer(body, np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), n_f, 4 * cols * n_v)
+    coloured = lines[6:-2][-3:] == rgb
+    cols = 3 + len(lines[6:-2]) - (3 if coloured else 0)
+    stride = 4 * cols + (3 if coloured else 0)
+    if n_v < 0 or n_f < 0 or len(body) != stride * n_v + 13 * n_f:
+        raise ValueError("%s: the body holds %d bytes, the header announces %d" % (path, len(body), stride * n_v + 13 * n_f))
+    table = np.frombuffer(body, np.dtype([("f", "<f4", (cols,))] + ([("c", "u1", (3,))] if coloured else [])), n_v)
+    v = table["f"].reshape(n_v, cols)
+    rows = np.frombuffer(body, np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), n_f, stride * n_v)
     if n_f and (rows["n"] != 3).any():
         raise ValueError("%s: a face that is not a triangle" % path)
     t = lambda a: torch.from_numpy(np.array(a))                        # a copy: the buffer is read-only
-    return Mesh(t(v[:, :3]), t(rows["idx"].astype(np.int32)), t(v[:, 3:]) if cols == 6 else None)
+    mesh = Mesh(t(v[:, :3]), t(rows["idx"].astype(np.int32)), t(v[:, 3:]) if cols == 6 else None)
+    if not return_colors:
+        return mesh
+    return mesh, (t(table["c"].reshape(n_v, 3).astype(np.float32) / np.float32(255.0)) if coloured else None)
 
 
-def read_obj(path):
+def read_obj(path, return_colors=False):
     """Reads exactly what write_obj writes -> Mesh of CPU tensors: `v x y z`, then `vn x y z` (as many as vertices) with `f a//a b//b
-    c//c`, or no normals with `f a b c`; `#` comments and blank lines are skipped.  Anything else raises ValueError."""
-    v, n, f = [], [], []
+    c//c`, or no normals with `f a b c`; `#` comments and blank lines are skipped.  Anything else raises ValueError.
+    return_colors=True: `v x y z r g b` lines are read too (every v line or none) -> (Mesh, colors f32 [V,3] or None); without it
+    such a line raises like any other line write_obj(path, mesh) does not produce."""
+    v, n, f, col = [], [], [], []
     with open(path) as fh:
         for no, line in enumerate(fh, 1):
             w = line.split()
             if not w or w[0].startswith("#"):
                 continue
             try:
-                if w[0] in ("v", "vn") and len(w) == 4:
+                if return_colors and w[0] == "v" and len(w) == 7:
+                    x = [float(s) for s in w[1:]]
+                    v.append(x[:3])
+                    col.append(x[3:])
+                elif w[0] in ("v", "vn") and len(w) == 4:
                     (v if w[0] == "v" else n).append([float(x) for x in w[1:]])
                 elif w[0] == "f" and len(w) == 4:
                     idx = []
@@ -526,5 +564,8 @@ def read_obj(path):
     faces = np.asarray(f, np.int64).reshape(-1, 3) - 1
     if len(faces) and (faces.min() < 0 or faces.max() >= len(v)):
         raise ValueError("%s: a face index outside 1..%d" % (path, len(v)))
+    if col and len(col) != len(v):
+        raise ValueError("%s: %d coloured vertices of %d" % (path, len(col), len(v)))
     t = lambda a, dt: torch.from_numpy(np.asarray(a, dt).reshape(-1, 3))
-    return Mesh(t(v, np.float32), torch.from_numpy(faces.astype(np.int32)), t(n, np.float32) if n else None)
+    mesh = Mesh(t(v, np.float32), torch.from_numpy(faces.astype(np.int32)), t(n, np.float32) if n else None)
+    return (mesh, t(col, np.float32) if col else None) if return_colors else mesh

@@ -326,7 +326,7 @@ def surface_distance(mesh_a, mesh_b, n=65536, generator=None, leaf_size=4):
     return out
 
 
-def render_mesh(target, K, c2w, img_wh, cull=None, smooth=None):
+def render_mesh(target, K, c2w, img_wh, cull=None, smooth=None, colors=None):
     """Depth, normal, mask and face images of a mesh seen from one camera: target a MeshSDF or a Mesh (a hierarchy is then built here,
     unsigned), K [3,3] intrinsics, c2w [3,4] (right, down, front | position), img_wh = (W, H) -> dict(depth [H,W] f32, normal [H,W,3]
     f32, mask [H,W] bool, face [H,W] int32).  The rays are those of get_ray_directions / get_rays, their directions normalised as
@@ -334,7 +334,9 @@ def render_mesh(target, K, c2w, img_wh, cull=None, smooth=None):
     render_surface_traced reports as `depth` and trace_surface as `t`, and what render() reports for unit directions -- so the images
     subtract directly where both hit.  Where the ray misses, depth is +inf (the traced renderers write 0 there): mask = isfinite(depth).
     normal: unit, towards the camera, the face's own or, with smooth = True (a Mesh's vertex normals) or a [V,3] tensor, interpolated;
-    0 on a miss.  cull as MeshSDF.raycast."""
+    0 on a miss.  cull as MeshSDF.raycast.  colors: per-vertex colours [V,3] (bake_image_colors, bake_field_colors); the result then
+    also holds rgb [H,W,3] f32, the colours of the hit face's corners a, b, c interpolated as a (1 - v - w) + b v + c w at the hit's
+    barycentrics, 0 on a miss."""
     from .rays import get_ray_directions, get_rays
     mesh_normals = getattr(target, "normals", None)
     if not isinstance(target, MeshSDF):
@@ -350,7 +352,16 @@ def render_mesh(target, K, c2w, img_wh, cull=None, smooth=None):
     rays_o, rays_d = get_rays(directions, torch.as_tensor(c2w, dtype=torch.float32).to(dev))
     rays_d = (rays_d / torch.linalg.norm(rays_d, dim=1, keepdim=True)).contiguous()
     hit = target.raycast(rays_o.contiguous(), rays_d, cull=cull)
-    return {"depth": hit.t.view(h, w), "normal": hit.normals(smooth).view(h, w, 3), "mask": hit.hit.view(h, w), "face": hit.face.view(h, w)}
+    out = {"depth": hit.t.view(h, w), "normal": hit.normals(smooth).view(h, w, 3), "mask": hit.hit.view(h, w), "face": hit.face.view(h, w)}
+    if colors is not None:
+        col = torch.as_tensor(colors, dtype=torch.float32, device=dev)
+        if tuple(col.shape) != tuple(target.vertices.shape):
+            raise ValueError("colors must hold one rgb triple per vertex, %s, got %s" % (tuple(target.vertices.shape), tuple(col.shape)))
+        corners = target.faces[hit.face.clamp_min(0).long()].long()
+        v, wb = hit.bary[:, :1], hit.bary[:, 1:]
+        rgb = col[corners[:, 0]] * (1.0 - v - wb) + col[corners[:, 1]] * v + col[corners[:, 2]] * wb
+        out["rgb"] = torch.where((hit.face >= 0)[:, None], rgb, torch.zeros_like(rgb)).view(h, w, 3)
+    return out
 
 
 __all__ = ["Mesh", "MeshDistance", "MeshRayHit", "MeshSDF", "morton_order", "pseudonormals", "render_mesh", "sample_surface", "surface_distance",

@@ -1312,6 +1312,103 @@ def mesh_vertex_normals(vertices, faces):
     return normals
 
 
+# ---------------------------------------------------------------------------------------------------- vertex colours
+MESH_COLOR_MODES = {"blend": _lib_mod._ABI.defines["NGP_MESH_COLOR_BLEND"], "best": _lib_mod._ABI.defines["NGP_MESH_COLOR_BEST"]}
+MESH_COLOR_PAIR_BYTES = 44              # per (vertex, camera) pair of a chunk: the segment 24, the sample 8, weight, cos and t 4 each
+MESH_COLOR_UNCOLOURED = 255             # `filled` of a vertex that has no colour
+
+
+def mesh_color_project(vertices, normals, K, c2w, img_wh, eps, cos_min=0.1, near=1e-6, two_sided=False):
+    """One chunk of cameras against every vertex (csrc/mesh_color.hip): vertices, normals f32 [V,3], K f32 [3,3] or [N,3,3], c2w f32
+    [N,3,4], eps f32 [1] ON THE DEVICE -> (rays_o [V N,3], rays_d [V N,3], sample [V N,2], weight [V N], cosv [V N]), pair j V + v.  A
+    rejected pair has weight 0 and a zero ray.  V >= 1, N >= 1, V N < 2^31."""
+    n_vertices = _mesh_arrays(vertices)[1]
+    for t, name in ((normals, "normals"), (K, "K"), (c2w, "c2w"), (eps, "eps")):
+        _dev(t, torch.float32, name)
+    if tuple(normals.shape) != tuple(vertices.shape):
+        raise ValueError("normals must be [V,3] like the vertices, got %s" % (tuple(normals.shape),))
+    if c2w.dim() != 3 or tuple(c2w.shape[1:]) != (3, 4) or tuple(K.shape) not in ((3, 3), (c2w.shape[0], 3, 3)) or eps.numel() != 1:
+        raise ValueError("c2w must be [N,3,4], K [3,3] or [N,3,3] and eps one element, got %s, %s, %s"
+                         % (tuple(c2w.shape), tuple(K.shape), tuple(eps.shape)))
+    n_cameras, (w, h) = int(c2w.shape[0]), (int(img_wh[0]), int(img_wh[1]))
+    pairs = n_vertices * n_cameras
+    if n_vertices < 1 or n_cameras < 1 or pairs >= 2**31 or w < 1 or h < 1:
+        raise ValueError("need V >= 1, N >= 1, V N < 2^31 and a positive image size, got V %d, N %d, (W, H) (%d, %d)" % (n_vertices, n_cameras, w, h))
+    if not float(cos_min) >= 0.0 or not float(near) >= 0.0:
+        raise ValueError("cos_min and near must be >= 0, got %r and %r" % (cos_min, near))
+    f32 = dict(device=vertices.device, dtype=torch.float32)
+    rays_o, rays_d, sample = torch.empty(pairs, 3, **f32), torch.empty(pairs, 3, **f32), torch.empty(pairs, 2, **f32)
+    weight, cosv = torch.empty(pairs, **f32), torch.empty(pairs, **f32)
+    check(_lib().ngp_mesh_color_project(_ptr(vertices), _ptr(normals), n_vertices, _ptr(K), int(K.dim() == 3), _ptr(c2w), n_cameras, w, h,
+                                        _ptr(eps), float(cos_min), float(near), int(bool(two_sided)), _ptr(rays_o), _ptr(rays_d),
+                                        _ptr(sample), _ptr(weight), _ptr(cosv), _stream()), "ngp_mesh_color_project")
+    return rays_o, rays_d, sample, weight, cosv
+
+
+def mesh_color_accumulate(images, sample, weight, cosv, t, accum, views, best_cos=None, mode="blend"):
+    """Adds one chunk into accum f64 [V,4] and views int32 [V] in place (best_cos f32 [V] too, mode "best"): images f32 [N,H,W,C >= 3] of
+    the chunk, sample / weight / cosv of mesh_color_project, t [V N] of the any-hit ray cast over its segments."""
+    if mode not in MESH_COLOR_MODES:
+        raise ValueError('mode must be "blend" or "best", got %r' % (mode,))
+    _dev(images, torch.float32, "images"); _dev(accum, torch.float64, "accum"); _dev(views, torch.int32, "views")
+    for x, name in ((sample, "sample"), (weight, "weight"), (cosv, "cosv"), (t, "t")):
+        _dev(x, torch.float32, name)
+    if images.dim() != 4 or images.shape[3] < 3 or images.shape[0] < 1:
+        raise ValueError("images must be [N,H,W,C] with C >= 3, got %s" % (tuple(images.shape),))
+    n_cameras, h, w, c = (int(x) for x in images.shape)
+    n_vertices = int(views.shape[0])
+    pairs = n_vertices * n_cameras
+    if tuple(accum.shape) != (n_vertices, 4) or views.dim() != 1 or n_vertices < 1 or pairs >= 2**31 \
+            or any(x.numel() != k * pairs for x, k in ((sample, 2), (weight, 1), (cosv, 1), (t, 1))):
+        raise ValueError("accum must be [V,4], views [V] and the per-pair arrays those of V x %d pairs" % n_cameras)
+    if mode == "best":
+        if best_cos is None or tuple(best_cos.shape) != (n_vertices,):
+            raise ValueError('mode "best" needs best_cos f32 [V]')
+        _dev(best_cos, torch.float32, "best_cos")
+    check(_lib().ngp_mesh_color_accumulate(_ptr(images), n_cameras, h, w, c, n_vertices, _ptr(sample), _ptr(weight), _ptr(cosv), _ptr(t),
+                                           MESH_COLOR_MODES[mode], _ptr(accum), _ptr(views), _ptr(best_cos if mode == "best" else None),
+                                           _stream()), "ngp_mesh_color_accumulate")
+    _touched(accum, views, best_cos if mode == "best" else None)
+
+
+def mesh_color_finish(accum, views):
+    """accum f64 [V,4], views int32 [V] -> (colors f32 [V,3], weight f32 [V], filled uint8 [V]: 0 where views > 0, else 255)."""
+    _dev(accum, torch.float64, "accum"); _dev(views, torch.int32, "views")
+    n_vertices = int(views.shape[0])
+    if tuple(accum.shape) != (n_vertices, 4) or views.dim() != 1:
+        raise ValueError("accum must be [V,4] and views [V]")
+    dev = accum.device
+    colors = torch.zeros(n_vertices, 3, device=dev, dtype=torch.float32)
+    weight = torch.zeros(n_vertices, device=dev, dtype=torch.float32)
+    filled = torch.full((n_vertices,), MESH_COLOR_UNCOLOURED, device=dev, dtype=torch.uint8)
+    if n_vertices:
+        check(_lib().ngp_mesh_color_finish(_ptr(accum), _ptr(views), n_vertices, _ptr(colors), _ptr(weight), _ptr(filled), _stream()),
+              "ngp_mesh_color_finish")
+    return colors, weight, filled
+
+
+def mesh_color_fill(colors, filled, row_start, neighbours, rounds):
+    """`rounds` Jacobi rounds (0 .. 254) over the CSR of mesh_adjacency: colors f32 [V,3] is updated IN PLACE, -> filled uint8 [V] after
+    the last round (the input tensor itself for rounds = 0).  No host read: every round is launched."""
+    _dev(colors, torch.float32, "colors"); _dev(filled, torch.uint8, "filled")
+    _dev(row_start, torch.int32, "row_start"); _dev(neighbours, torch.int32, "neighbours")
+    n_vertices = int(filled.shape[0])
+    rounds = int(rounds)
+    if tuple(colors.shape) != (n_vertices, 3) or tuple(row_start.shape) != (n_vertices + 1,) or neighbours.dim() != 1:
+        raise ValueError("colors must be [V,3], filled [V], row_start [V + 1] and neighbours [E]")
+    if not 0 <= rounds < MESH_COLOR_UNCOLOURED:
+        raise ValueError("rounds must be in 0..254, got %r" % (rounds,))
+    if n_vertices == 0 or neighbours.shape[0] == 0:
+        return filled
+    other = torch.empty_like(filled) if rounds else None
+    for r in range(1, rounds + 1):
+        check(_lib().ngp_mesh_color_fill(_ptr(colors), _ptr(filled), _ptr(other), _ptr(row_start), _ptr(neighbours), n_vertices,
+                                         int(neighbours.shape[0]), r, _stream()), "ngp_mesh_color_fill")
+        filled, other = other, filled
+    _touched(colors)
+    return filled
+
+
 # ---------------------------------------------------------------------------------------------------- surface rendering
 def _surface_inputs(sdf, cosv, rgbs, aux, deltas, ts, rays_a, inv_s):
     _dev(sdf, torch.float32, "sdf"); _dev(cosv, torch.float32, "cosv"); _dev(rgbs, torch.float32, "rgbs")
