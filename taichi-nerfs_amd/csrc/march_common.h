@@ -104,12 +104,6 @@ __device__ __forceinline__ float2 ray_aabb_slab(const float o[3], const float d_
     return (a2 > 0.0f) ? make_float2(fmaxf(a1, 0.01f), a2) : make_float2(-1.0f, -1.0f);
 }
 
-// LDS traffic between the lanes of ONE wave: order it for the compiler and the memory pipeline, no block barrier
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 constexpr int MARCH_MAX_COARSE_WORDS = 1024;            // 32 768 coarse blocks: up to 8 cascades of a 128^3 grid
 constexpr int ORBIT_BATCH = 8;      // orbit points probed speculatively per iteration by the kernels with one lane per ray
 

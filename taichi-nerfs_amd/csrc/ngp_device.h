@@ -145,6 +145,12 @@ __device__ __forceinline__ float fsign(float x) { return (float)((x > 0.0f) - (x
 // ---- wave64 primitives -------------------------------------------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & (NGP_WAVE - 1)); }
 
+// LDS traffic between the lanes of ONE wave: order it for the compiler and the memory pipeline, no block barrier
+__device__ __forceinline__ void wave_sync_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, NGP_WAVE);

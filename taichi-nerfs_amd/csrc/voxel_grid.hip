@@ -23,6 +23,18 @@
 //                             beside each lane's row vector in LDS; runs of equal base CELL are summed per (corner, channel) before
 //                             any atomic, and the adds of a z-pair of corners form one contiguous 2 x 12 D-byte segment of dsh
 //   voxel_occ_*           packbits for the occupancy grid with the mean accumulated in f64 and `>=` (the fresh-field trap)
+// Shared by the nearest and the trilinear form, each stated once:
+//   vox_row_values        a row's forward value: the raw density and the three dot products sum_k Y[k] sh[c * D + k] (nearest: its one
+//                         row; trilinear: each of the eight corners); vox_relu / vox_sigmoid are the two activations
+//   vox_trilerp           the lerp tree z, then y, then x over eight corner values (trilinear forward per channel, trilinear density)
+//   vox_grad_row          the backward preamble: the sample's four gradients, the all-zero skip, lane's tile row g[c] * Y[k] | gs
+//   vox_find_runs         runs of equal keys (row or base cell) among a wave's 64 lanes as two ballots, `starts` (every run) and `heads`
+//                         (runs of a key >= 0), then the wave-level ordering of the tile writes before the merge reads them
+//   vox_take_heads / vox_run_end   the merge loop's "next PER heads, one per slot" and "[h, next boundary)"
+//   vox_cell_key / vox_key_cell    the trilinear run key of base cell b in [-1, G)^3 and its inverse
+//   vox_launch / vox_for_degree    the host entries' prologue (n, grid parameters, launch check) and the degree dispatch of the four
+//                                  templated kernels; each nearest / trilinear entry pair is one function that picks the kernel
+#include <type_traits>
 #include "ngp_device.h"
 
 namespace ngp {
@@ -88,6 +100,23 @@ __device__ __forceinline__ void sh_basis(const float* __restrict__ dirs, long i,
     }
 }
 
+__device__ __forceinline__ float vox_relu(float v) { return v > 0.0f ? v : 0.0f; }
+__device__ __forceinline__ float vox_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// out[0] = the raw density of `row`, out[1 + c] = sum_k Y[k] * sh[row][c * D + k] in index order; all zero for row < 0
+template <int DEG>
+__device__ __forceinline__ void vox_row_values(long long row, const float* Y, const float* density, const float* sh, float out[4]) {
+    constexpr int D = (DEG + 1) * (DEG + 1);
+    out[0] = out[1] = out[2] = out[3] = 0.0f;
+    if (row < 0) return;
+    out[0] = density[row];
+    const float* s = sh + (size_t)row * (3 * D);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < D; ++k) out[1 + c] += Y[k] * s[c * D + k];
+}
+
 template <int DEG>
 __global__ void __launch_bounds__(256) voxel_fwd_kernel(const float* __restrict__ xyzs, const float* __restrict__ dirs,
                                                         const float* __restrict__ sh, const float* __restrict__ density, int n,
@@ -96,21 +125,12 @@ __global__ void __launch_bounds__(256) voxel_fwd_kernel(const float* __restrict_
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const long long row = vox_row(vp, xyzs, i);
-    float Y[D];
+    float Y[D], v[4];
     sh_basis<DEG>(dirs, i, Y);
-    float sigma = 0.0f, acc[3] = {0.0f, 0.0f, 0.0f};
-    if (row >= 0) {
-        const float dv = density[row];
-        sigma = dv > 0.0f ? dv : 0.0f;
-        const float* s = sh + (size_t)row * (3 * D);
+    vox_row_values<DEG>(row, Y, density, sh, v);
+    sigmas[i] = vox_relu(v[0]);
 #pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int k = 0; k < D; ++k) acc[c] += Y[k] * s[c * D + k];
-    }
-    sigmas[i] = sigma;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) rgbs[i * 3 + c] = 1.0f / (1.0f + expf(-acc[c]));
+    for (int c = 0; c < 3; ++c) rgbs[i * 3 + c] = vox_sigmoid(v[1 + c]);
 }
 
 __global__ void __launch_bounds__(256) voxel_density_kernel(const float* __restrict__ xyzs, const float* __restrict__ density, int n,
@@ -118,12 +138,70 @@ __global__ void __launch_bounds__(256) voxel_density_kernel(const float* __restr
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const long long row = vox_row(vp, xyzs, i);
-    const float dv = row >= 0 ? density[row] : 0.0f;
-    sigmas[i] = dv > 0.0f ? dv : 0.0f;
+    sigmas[i] = vox_relu(row >= 0 ? density[row] : 0.0f);
 }
 
-// d sigma / d density = [density > 0] (= [sigma > 0]); d rgb_c / d sh_{c,k} = rgb_c (1 - rgb_c) Y_k.  Tile column c*D + k holds the
-// SH contribution, column 3*D the density one.
+// ---------------------------------------------------------------------------------------------------- backward, both forms
+// d sigma / d density = [density > 0] (= [sigma > 0]); d rgb_c / d sh_{c,k} = rgb_c (1 - rgb_c) Y_k.  Writes sample i's row of the
+// wave's tile (column c*D + k the SH contribution, column 3*D the density one) unless all four gradients are zero: false then, the
+// sample contributes nothing.
+template <int DEG>
+__device__ __forceinline__ bool vox_grad_row(const float* __restrict__ dirs, const float* __restrict__ sigmas, const float* __restrict__ rgbs,
+                                             const float* __restrict__ dsigmas, const float* __restrict__ drgbs, long i, float* trow) {
+    constexpr int D = (DEG + 1) * (DEG + 1);
+    const float gs = sigmas[i] > 0.0f ? dsigmas[i] : 0.0f;
+    float g[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float o = rgbs[i * 3 + c];
+        g[c] = drgbs[i * 3 + c] * (o * (1.0f - o));
+    }
+    if (gs == 0.0f && g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) return false;
+    float Y[D];
+    sh_basis<DEG>(dirs, i, Y);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < D; ++k) trow[c * D + k] = g[c] * Y[k];
+    trow[3 * D] = gs;
+    return true;
+}
+
+// Runs of equal keys among the wave's lanes: a boundary wherever the key changes.  `starts` has every run's first lane, `heads` those
+// of the runs to flush (key >= 0).  Ends with the ordering of the lanes' tile writes before the merge loops read other lanes' rows.
+struct VoxRuns {
+    unsigned long long starts, heads;
+};
+__device__ __forceinline__ VoxRuns vox_find_runs(long long key, int lane) {
+    const long long prev = __shfl_up(key, 1);
+    const bool boundary = lane == 0 || prev != key;
+    const VoxRuns r = {__ballot(boundary), __ballot(boundary && key >= 0)};
+    wave_sync_lds();
+    return r;
+}
+
+// the next PER run heads of `heads` (removed from it): slot s gets the s-th, -1 when there is none
+template <int PER>
+__device__ __forceinline__ int vox_take_heads(unsigned long long& heads, int slot) {
+    unsigned long long rest = heads;
+    int h = -1;
+#pragma unroll
+    for (int s = 0; s < PER; ++s) {
+        const int hs = rest ? __ffsll((long long)rest) - 1 : -1;
+        if (s == slot) h = hs;
+        if (rest) rest &= rest - 1ull;
+    }
+    heads = rest;
+    return h;
+}
+
+// the run that starts at lane h is [h, next boundary)
+__device__ __forceinline__ int vox_run_end(unsigned long long starts, int h) {
+    const unsigned long long after = h == 63 ? 0ull : (starts >> (h + 1)) << (h + 1);
+    return after ? __ffsll((long long)after) - 1 : NGP_WAVE;
+}
+
+// One wave per 64 consecutive samples; runs of equal ROW are summed per channel before any atomic (header).
 template <int DEG>
 __global__ void __launch_bounds__(64 * VOX_BWD_WAVES) voxel_bwd_kernel(const float* __restrict__ xyzs, const float* __restrict__ dirs,
                                                                       const float* __restrict__ sigmas, const float* __restrict__ rgbs,
@@ -139,59 +217,22 @@ __global__ void __launch_bounds__(64 * VOX_BWD_WAVES) voxel_bwd_kernel(const flo
     long long row = -1;
     if (i < n) {
         row = vox_row(vp, xyzs, i);
-        if (row >= 0) {
-            const float gs = sigmas[i] > 0.0f ? dsigmas[i] : 0.0f;
-            float g[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float o = rgbs[i * 3 + c];
-                g[c] = drgbs[i * 3 + c] * (o * (1.0f - o));
-            }
-            if (gs == 0.0f && g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) {
-                row = -1;                                                  // contributes nothing
-            } else {
-                float Y[D];
-                sh_basis<DEG>(dirs, i, Y);
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int k = 0; k < D; ++k) T[lane][c * D + k] = g[c] * Y[k];
-                T[lane][3 * D] = gs;
-            }
-        }
+        if (row >= 0 && !vox_grad_row<DEG>(dirs, sigmas, rgbs, dsigmas, drgbs, i, T[lane])) row = -1;
     }
-    // runs of equal rows: a boundary wherever the row changes; only runs of a valid row are flushed
-    const long long prev = __shfl_up(row, 1);
-    const bool boundary = lane == 0 || prev != row;
-    const unsigned long long starts = __ballot(boundary);
-    unsigned long long heads = __ballot(boundary && row >= 0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const int slot = lane / W, ch = lane - slot * W;
-    while (heads) {
-        // the next PER runs: slot s takes the s-th remaining head
-        unsigned long long rest = heads;
-        int h = -1;
-#pragma unroll
-        for (int s = 0; s < PER; ++s) {
-            const int hs = rest ? __ffsll((long long)rest) - 1 : -1;
-            if (s == slot) h = hs;
-            if (rest) rest &= rest - 1ull;
-        }
-        heads = rest;
+    const VoxRuns runs = vox_find_runs(row, lane);
+    const int slot = lane / W, ch = lane % W;                         // (%: ch < W is then known and the column loop folds for W < 64)
+    unsigned long long hd = runs.heads;
+    while (hd) {
+        const int h = vox_take_heads<PER>(hd, slot);
         const long long hrow = __shfl(row, h < 0 ? 0 : h);           // every lane takes part in the shuffle
-        if (slot < PER && h >= 0) {
-            // the run is [h, next boundary)
-            const unsigned long long after = h == 63 ? 0ull : (starts >> (h + 1)) << (h + 1);
-            const int end = after ? __ffsll((long long)after) - 1 : NGP_WAVE;
-            for (int c0 = ch; c0 < W; c0 += (W < NGP_WAVE ? W : NGP_WAVE)) {
-                float v = 0.0f;
-                for (int s = h; s < end; ++s) v += T[s][c0];
-                if (v != 0.0f) {
-                    if (c0 < 3 * D) unsafeAtomicAdd(dsh + (size_t)hrow * (3 * D) + c0, v);
-                    else unsafeAtomicAdd(ddensity + hrow, v);
-                }
+        if (h < 0) continue;                                         // also the lanes past the last whole row: slot >= PER
+        const int end = vox_run_end(runs.starts, h);
+        for (int c0 = ch; c0 < W; c0 += (W < NGP_WAVE ? W : NGP_WAVE)) {
+            float v = 0.0f;
+            for (int s = h; s < end; ++s) v += T[s][c0];
+            if (v != 0.0f) {
+                if (c0 < 3 * D) unsafeAtomicAdd(dsh + (size_t)hrow * (3 * D) + c0, v);
+                else unsafeAtomicAdd(ddensity + hrow, v);
             }
         }
     }
@@ -224,6 +265,26 @@ __device__ __forceinline__ long long vox_corner_row(const VoxParams& vp, const i
 // trilinear_interpolation's lerp (:524-533).  This form, not (1 - t) a + t b, returns a constant field exactly.
 __device__ __forceinline__ float vox_lerp(float a, float b, float t) { return a + t * (b - a); }
 
+// the nested lerps over the eight corner values: along z, then y, then x
+__device__ __forceinline__ float vox_trilerp(const float v[8], const float f[3]) {
+    float z[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) z[p] = vox_lerp(v[2 * p], v[2 * p + 1], f[2]);
+    return vox_lerp(vox_lerp(z[0], z[1], f[1]), vox_lerp(z[2], z[3], f[1]), f[0]);
+}
+
+// the trilinear backward's run key of base cell b, every axis in [-1, G): ((bx + 1) (G + 1) + by + 1) (G + 1) + bz + 1, and back
+__device__ __forceinline__ long long vox_cell_key(const VoxParams& vp, const int b[3]) {
+    const int G1 = vp.G + 1;
+    return ((long long)(b[0] + 1) * G1 + (b[1] + 1)) * G1 + (b[2] + 1);
+}
+__device__ __forceinline__ void vox_key_cell(const VoxParams& vp, long long key, int b[3]) {
+    const int G1 = vp.G + 1;
+    b[0] = (int)(key / ((long long)G1 * G1)) - 1;
+    b[1] = (int)((key / G1) % G1) - 1;
+    b[2] = (int)(key % G1) - 1;
+}
+
 // One lane per sample: per corner the density and the three dot products sum_k Y_k sh_{c,k} (eval_sh is linear), then the lerps.
 template <int DEG>
 __global__ void __launch_bounds__(256) voxel_tri_fwd_kernel(const float* __restrict__ xyzs, const float* __restrict__ dirs,
@@ -234,34 +295,20 @@ __global__ void __launch_bounds__(256) voxel_tri_fwd_kernel(const float* __restr
     if (i >= n) return;
     int b[3];
     float f[3];
-    float v[8][4];
+    float v[4][8];                                                       // [density | R, G, B dot product][corner]
     const bool in = vox_cell(vp, xyzs, i, b, f);
     float Y[D];
     sh_basis<DEG>(dirs, i, Y);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const long long row = in ? vox_corner_row(vp, b, c) : -1;
-        v[c][0] = v[c][1] = v[c][2] = v[c][3] = 0.0f;
-        if (row >= 0) {
-            v[c][0] = density[row];
-            const float* s = sh + (size_t)row * (3 * D);
+        float r[4];
+        vox_row_values<DEG>(in ? vox_corner_row(vp, b, c) : -1, Y, density, sh, r);
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-                for (int k = 0; k < D; ++k) v[c][1 + ch] += Y[k] * s[ch * D + k];
-        }
+        for (int q = 0; q < 4; ++q) v[q][c] = r[q];
     }
-    float o[4];
+    sigmas[i] = vox_relu(vox_trilerp(v[0], f));
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float z[4];
-#pragma unroll
-        for (int p = 0; p < 4; ++p) z[p] = vox_lerp(v[2 * p][q], v[2 * p + 1][q], f[2]);
-        o[q] = vox_lerp(vox_lerp(z[0], z[1], f[1]), vox_lerp(z[2], z[3], f[1]), f[0]);
-    }
-    sigmas[i] = o[0] > 0.0f ? o[0] : 0.0f;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) rgbs[i * 3 + ch] = 1.0f / (1.0f + expf(-o[1 + ch]));
+    for (int ch = 0; ch < 3; ++ch) rgbs[i * 3 + ch] = vox_sigmoid(vox_trilerp(v[1 + ch], f));
 }
 
 __global__ void __launch_bounds__(256) voxel_tri_density_kernel(const float* __restrict__ xyzs, const float* __restrict__ density, int n,
@@ -278,38 +325,13 @@ __global__ void __launch_bounds__(256) voxel_tri_density_kernel(const float* __r
             const long long row = vox_corner_row(vp, b, c);
             v[c] = row >= 0 ? density[row] : 0.0f;
         }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = vox_lerp(v[2 * c], v[2 * c + 1], f[2]);
-        v[0] = vox_lerp(v[0], v[1], f[1]);
-        v[1] = vox_lerp(v[2], v[3], f[1]);
-        dv = vox_lerp(v[0], v[1], f[0]);
+        dv = vox_trilerp(v, f);
     }
-    sigmas[i] = dv > 0.0f ? dv : 0.0f;
-}
-
-// the next PER run heads of `heads` (removed from it): slot s gets the s-th, -1 when there is none
-template <int PER>
-__device__ __forceinline__ int vox_take_heads(unsigned long long& heads, int slot) {
-    unsigned long long rest = heads;
-    int h = -1;
-#pragma unroll
-    for (int s = 0; s < PER; ++s) {
-        const int hs = rest ? __ffsll((long long)rest) - 1 : -1;
-        if (s == slot) h = hs;
-        if (rest) rest &= rest - 1ull;
-    }
-    heads = rest;
-    return h;
-}
-
-// the run that starts at lane h is [h, next boundary)
-__device__ __forceinline__ int vox_run_end(unsigned long long starts, int h) {
-    const unsigned long long after = h == 63 ? 0ull : (starts >> (h + 1)) << (h + 1);
-    return after ? __ffsll((long long)after) - 1 : NGP_WAVE;
+    sigmas[i] = vox_relu(dv);
 }
 
 // d out / d row[corner] = w_corner * (d out / d interpolated row), w_corner the product of the per-axis factors (1 - f or f).  Tile
-// columns as in voxel_bwd_kernel; wts[lane][corner] beside them.  A run is a stretch of lanes with the same base cell: all its samples
+// columns as vox_grad_row writes them; wts[lane][corner] beside them.  A run is a stretch of lanes with the same base cell: all its samples
 // add into the same eight rows.  SH: a z-pair of corners (rows r and r + 1) is one segment of SEG = 6 D consecutive floats of dsh; NS
 // segments fit one atomic instruction (degree 0: 2 runs x 4 pairs, degree 1: 2 pairs, degree 2: 1; degrees 3, 4: a column loop).
 // Density: 8 lanes per run, z on the lowest lane bit, 8 runs per atomic instruction.
@@ -330,51 +352,29 @@ __global__ void __launch_bounds__(64 * VOX_BWD_WAVES) voxel_tri_bwd_kernel(const
     float (*T)[W] = tile[wv];
     float (*Wt)[8] = wts[wv];
     const long i = ((long)blockIdx.x * VOX_BWD_WAVES + wv) * NGP_WAVE + lane;
-    const int G1 = vp.G + 1;
-    long long cell = -1;                                                 // ((bx + 1) (G + 1) + by + 1) (G + 1) + bz + 1, b in [-1, G)
+    long long cell = -1;                                                 // vox_cell_key of a contributing sample
     if (i < n) {
         int b[3];
         float f[3];
-        if (vox_cell(vp, xyzs, i, b, f)) {
-            const float gs = sigmas[i] > 0.0f ? dsigmas[i] : 0.0f;
-            float g[3];
+        if (vox_cell(vp, xyzs, i, b, f) && vox_grad_row<DEG>(dirs, sigmas, rgbs, dsigmas, drgbs, i, T[lane])) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float o = rgbs[i * 3 + c];
-                g[c] = drgbs[i * 3 + c] * (o * (1.0f - o));
-            }
-            if (!(gs == 0.0f && g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f)) {
-                float Y[D];
-                sh_basis<DEG>(dirs, i, Y);
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int k = 0; k < D; ++k) T[lane][c * D + k] = g[c] * Y[k];
-                T[lane][3 * D] = gs;
-#pragma unroll
-                for (int c = 0; c < 8; ++c)
-                    Wt[lane][c] = ((c & 4) ? f[0] : 1.0f - f[0]) * ((c & 2) ? f[1] : 1.0f - f[1]) * ((c & 1) ? f[2] : 1.0f - f[2]);
-                cell = ((long long)(b[0] + 1) * G1 + (b[1] + 1)) * G1 + (b[2] + 1);
-            }
+            for (int c = 0; c < 8; ++c)
+                Wt[lane][c] = ((c & 4) ? f[0] : 1.0f - f[0]) * ((c & 2) ? f[1] : 1.0f - f[1]) * ((c & 1) ? f[2] : 1.0f - f[2]);
+            cell = vox_cell_key(vp, b);
         }
     }
-    const long long prev = __shfl_up(cell, 1);
-    const bool boundary = lane == 0 || prev != cell;
-    const unsigned long long starts = __ballot(boundary);
-    const unsigned long long heads = __ballot(boundary && cell >= 0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const VoxRuns runs = vox_find_runs(cell, lane);
     // ---- SH coefficients
     {
         const int slot = lane / LW, col0 = lane - slot * LW, rslot = slot / PP, pslot = slot - rslot * PP;
-        unsigned long long hd = heads;
+        unsigned long long hd = runs.heads;
         while (hd) {
             const int h = vox_take_heads<RP>(hd, rslot);                 // lanes past the last whole segment: rslot >= RP, h = -1
             const long long hcell = __shfl(cell, h < 0 ? 0 : h);         // every lane takes part in the shuffle
             if (h < 0) continue;
-            const int end = vox_run_end(starts, h);
-            const int b[3] = {(int)(hcell / ((long long)G1 * G1)) - 1, (int)((hcell / G1) % G1) - 1, (int)(hcell % G1) - 1};
+            const int end = vox_run_end(runs.starts, h);
+            int b[3];
+            vox_key_cell(vp, hcell, b);
             for (int p = pslot; p < 4; p += PP)
                 for (int col = col0; col < SEG; col += LW) {
                     const int k = col >= 3 * D ? 1 : 0, c0 = col - k * (3 * D), corner = 2 * p + k;
@@ -389,13 +389,14 @@ __global__ void __launch_bounds__(64 * VOX_BWD_WAVES) voxel_tri_bwd_kernel(const
     // ---- density
     {
         const int rslot = lane >> 3, corner = lane & 7;
-        unsigned long long hd = heads;
+        unsigned long long hd = runs.heads;
         while (hd) {
             const int h = vox_take_heads<8>(hd, rslot);
             const long long hcell = __shfl(cell, h < 0 ? 0 : h);
             if (h < 0) continue;
-            const int end = vox_run_end(starts, h);
-            const int b[3] = {(int)(hcell / ((long long)G1 * G1)) - 1, (int)((hcell / G1) % G1) - 1, (int)(hcell % G1) - 1};
+            const int end = vox_run_end(runs.starts, h);
+            int b[3];
+            vox_key_cell(vp, hcell, b);
             const long long row = vox_corner_row(vp, b, corner);
             if (row < 0) continue;
             float v = 0.0f;
@@ -449,10 +450,61 @@ __global__ void __launch_bounds__(256) voxel_occ_pack_kernel(const float* __rest
     }
 }
 
-static bool vox_params(int grid_size, float grid_min, float grid_radius, VoxParams& vp) {
-    if (grid_size < 1 || grid_size > 1024 || !(grid_radius > 0.0f)) return false;
-    vp = VoxParams{grid_size, grid_min, grid_radius};
-    return true;
+// ---------------------------------------------------------------------------------------------------- host entries
+// The prologue and epilogue of every per-sample entry: nothing to do for n <= 0, -1 for bad grid parameters or when `launch` (which
+// gets the VoxParams and returns whether it launched) refuses, the launch's error otherwise.
+template <class Launch>
+static int vox_launch(int n, int grid_size, float grid_min, float grid_radius, Launch&& launch) {
+    if (n <= 0) return 0;
+    if (grid_size < 1 || grid_size > 1024 || !(grid_radius > 0.0f)) return -1;
+    if (!launch(VoxParams{grid_size, grid_min, grid_radius})) return -1;
+    NGP_LAUNCH_CHECK();
+    return 0;
+}
+
+// f(std::integral_constant<int, DEG>) for the sh_degree the kernels are instantiated for; false for any other
+template <class F>
+static bool vox_for_degree(int sh_degree, F&& f) {
+    switch (sh_degree) {
+        case 0: f(std::integral_constant<int, 0>()); return true;
+        case 1: f(std::integral_constant<int, 1>()); return true;
+        case 2: f(std::integral_constant<int, 2>()); return true;
+        case 3: f(std::integral_constant<int, 3>()); return true;
+        case 4: f(std::integral_constant<int, 4>()); return true;
+        default: return false;
+    }
+}
+
+static int vox_fwd(bool trilinear, const float* xyzs, const float* dirs, const float* sh, const float* density, int n, int grid_size,
+                   int sh_degree, float grid_min, float grid_radius, float* sigmas, float* rgbs, void* stream) {
+    return vox_launch(n, grid_size, grid_min, grid_radius, [&](const VoxParams& vp) {
+        return vox_for_degree(sh_degree, [&](auto deg) {
+            constexpr int DEG = decltype(deg)::value;
+            hipLaunchKernelGGL(trilinear ? voxel_tri_fwd_kernel<DEG> : voxel_fwd_kernel<DEG>, dim3((n + 255) / 256), dim3(256), 0,
+                               (hipStream_t)stream, xyzs, dirs, sh, density, n, vp, sigmas, rgbs);
+        });
+    });
+}
+
+static int vox_density(bool trilinear, const float* xyzs, const float* density, int n, int grid_size, float grid_min, float grid_radius,
+                       float* sigmas, void* stream) {
+    return vox_launch(n, grid_size, grid_min, grid_radius, [&](const VoxParams& vp) {
+        hipLaunchKernelGGL(trilinear ? voxel_tri_density_kernel : voxel_density_kernel, dim3((n + 255) / 256), dim3(256), 0,
+                           (hipStream_t)stream, xyzs, density, n, vp, sigmas);
+        return true;
+    });
+}
+
+static int vox_bwd(bool trilinear, const float* xyzs, const float* dirs, const float* sigmas, const float* rgbs, const float* dsigmas,
+                   const float* drgbs, int n, int grid_size, int sh_degree, float grid_min, float grid_radius, float* dsh, float* ddensity,
+                   void* stream) {
+    return vox_launch(n, grid_size, grid_min, grid_radius, [&](const VoxParams& vp) {
+        return vox_for_degree(sh_degree, [&](auto deg) {
+            constexpr int DEG = decltype(deg)::value, per_block = 64 * VOX_BWD_WAVES;
+            hipLaunchKernelGGL(trilinear ? voxel_tri_bwd_kernel<DEG> : voxel_bwd_kernel<DEG>, dim3((n + per_block - 1) / per_block),
+                               dim3(per_block), 0, (hipStream_t)stream, xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, n, vp, dsh, ddensity);
+        });
+    });
 }
 
 }  // namespace ngp
@@ -463,109 +515,33 @@ extern "C" {
 
 int ngp_voxel_fwd(const float* xyzs, const float* dirs, const float* sh, const float* density, int n, int grid_size, int sh_degree,
                   float grid_min, float grid_radius, float* sigmas, float* rgbs, void* stream) {
-    if (n <= 0) return 0;
-    VoxParams vp;
-    if (!vox_params(grid_size, grid_min, grid_radius, vp)) return -1;
-    const dim3 grid((n + 255) / 256), block(256);
-    hipStream_t st = (hipStream_t)stream;
-    switch (sh_degree) {
-        case 0: hipLaunchKernelGGL(voxel_fwd_kernel<0>, grid, block, 0, st, xyzs, dirs, sh, density, n, vp, sigmas, rgbs); break;
-        case 1: hipLaunchKernelGGL(voxel_fwd_kernel<1>, grid, block, 0, st, xyzs, dirs, sh, density, n, vp, sigmas, rgbs); break;
-        case 2: hipLaunchKernelGGL(voxel_fwd_kernel<2>, grid, block, 0, st, xyzs, dirs, sh, density, n, vp, sigmas, rgbs); break;
-        case 3: hipLaunchKernelGGL(voxel_fwd_kernel<3>, grid, block, 0, st, xyzs, dirs, sh, density, n, vp, sigmas, rgbs); break;
-        case 4: hipLaunchKernelGGL(voxel_fwd_kernel<4>, grid, block, 0, st, xyzs, dirs, sh, density, n, vp, sigmas, rgbs); break;
-        default: return -1;
-    }
-    NGP_LAUNCH_CHECK();
-    return 0;
-}
-
-int ngp_voxel_density(const float* xyzs, const float* density, int n, int grid_size, float grid_min, float grid_radius, float* sigmas,
-                      void* stream) {
-    if (n <= 0) return 0;
-    VoxParams vp;
-    if (!vox_params(grid_size, grid_min, grid_radius, vp)) return -1;
-    hipLaunchKernelGGL(voxel_density_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, xyzs, density, n, vp, sigmas);
-    NGP_LAUNCH_CHECK();
-    return 0;
-}
-
-int ngp_voxel_bwd(const float* xyzs, const float* dirs, const float* sigmas, const float* rgbs, const float* dsigmas, const float* drgbs,
-                  int n, int grid_size, int sh_degree, float grid_min, float grid_radius, float* dsh, float* ddensity, void* stream) {
-    if (n <= 0) return 0;
-    VoxParams vp;
-    if (!vox_params(grid_size, grid_min, grid_radius, vp)) return -1;
-    const int per_block = 64 * VOX_BWD_WAVES;
-    const dim3 grid((n + per_block - 1) / per_block), block(per_block);
-    hipStream_t st = (hipStream_t)stream;
-#define NGP_VOX_BWD(DEG) hipLaunchKernelGGL(voxel_bwd_kernel<DEG>, grid, block, 0, st, xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, n, vp, dsh, \
-                                            ddensity)
-    switch (sh_degree) {
-        case 0: NGP_VOX_BWD(0); break;
-        case 1: NGP_VOX_BWD(1); break;
-        case 2: NGP_VOX_BWD(2); break;
-        case 3: NGP_VOX_BWD(3); break;
-        case 4: NGP_VOX_BWD(4); break;
-        default: return -1;
-    }
-#undef NGP_VOX_BWD
-    NGP_LAUNCH_CHECK();
-    return 0;
+    return vox_fwd(false, xyzs, dirs, sh, density, n, grid_size, sh_degree, grid_min, grid_radius, sigmas, rgbs, stream);
 }
 
 int ngp_voxel_trilinear_fwd(const float* xyzs, const float* dirs, const float* sh, const float* density, int n, int grid_size,
                             int sh_degree, float grid_min, float grid_radius, float* sigmas, float* rgbs, void* stream) {
-    if (n <= 0) return 0;
-    VoxParams vp;
-    if (!vox_params(grid_size, grid_min, grid_radius, vp)) return -1;
-    const dim3 grid((n + 255) / 256), block(256);
-    hipStream_t st = (hipStream_t)stream;
-#define NGP_VOX_TRI_FWD(DEG) hipLaunchKernelGGL(voxel_tri_fwd_kernel<DEG>, grid, block, 0, st, xyzs, dirs, sh, density, n, vp, sigmas, rgbs)
-    switch (sh_degree) {
-        case 0: NGP_VOX_TRI_FWD(0); break;
-        case 1: NGP_VOX_TRI_FWD(1); break;
-        case 2: NGP_VOX_TRI_FWD(2); break;
-        case 3: NGP_VOX_TRI_FWD(3); break;
-        case 4: NGP_VOX_TRI_FWD(4); break;
-        default: return -1;
-    }
-#undef NGP_VOX_TRI_FWD
-    NGP_LAUNCH_CHECK();
-    return 0;
+    return vox_fwd(true, xyzs, dirs, sh, density, n, grid_size, sh_degree, grid_min, grid_radius, sigmas, rgbs, stream);
+}
+
+int ngp_voxel_density(const float* xyzs, const float* density, int n, int grid_size, float grid_min, float grid_radius, float* sigmas,
+                      void* stream) {
+    return vox_density(false, xyzs, density, n, grid_size, grid_min, grid_radius, sigmas, stream);
 }
 
 int ngp_voxel_trilinear_density(const float* xyzs, const float* density, int n, int grid_size, float grid_min, float grid_radius,
                                 float* sigmas, void* stream) {
-    if (n <= 0) return 0;
-    VoxParams vp;
-    if (!vox_params(grid_size, grid_min, grid_radius, vp)) return -1;
-    hipLaunchKernelGGL(voxel_tri_density_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, xyzs, density, n, vp, sigmas);
-    NGP_LAUNCH_CHECK();
-    return 0;
+    return vox_density(true, xyzs, density, n, grid_size, grid_min, grid_radius, sigmas, stream);
+}
+
+int ngp_voxel_bwd(const float* xyzs, const float* dirs, const float* sigmas, const float* rgbs, const float* dsigmas, const float* drgbs,
+                  int n, int grid_size, int sh_degree, float grid_min, float grid_radius, float* dsh, float* ddensity, void* stream) {
+    return vox_bwd(false, xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, n, grid_size, sh_degree, grid_min, grid_radius, dsh, ddensity, stream);
 }
 
 int ngp_voxel_trilinear_bwd(const float* xyzs, const float* dirs, const float* sigmas, const float* rgbs, const float* dsigmas,
                             const float* drgbs, int n, int grid_size, int sh_degree, float grid_min, float grid_radius, float* dsh,
                             float* ddensity, void* stream) {
-    if (n <= 0) return 0;
-    VoxParams vp;
-    if (!vox_params(grid_size, grid_min, grid_radius, vp)) return -1;
-    const int per_block = 64 * VOX_BWD_WAVES;
-    const dim3 grid((n + per_block - 1) / per_block), block(per_block);
-    hipStream_t st = (hipStream_t)stream;
-#define NGP_VOX_TRI_BWD(DEG) hipLaunchKernelGGL(voxel_tri_bwd_kernel<DEG>, grid, block, 0, st, xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, n, vp, \
-                                                dsh, ddensity)
-    switch (sh_degree) {
-        case 0: NGP_VOX_TRI_BWD(0); break;
-        case 1: NGP_VOX_TRI_BWD(1); break;
-        case 2: NGP_VOX_TRI_BWD(2); break;
-        case 3: NGP_VOX_TRI_BWD(3); break;
-        case 4: NGP_VOX_TRI_BWD(4); break;
-        default: return -1;
-    }
-#undef NGP_VOX_TRI_BWD
-    NGP_LAUNCH_CHECK();
-    return 0;
+    return vox_bwd(true, xyzs, dirs, sigmas, rgbs, dsigmas, drgbs, n, grid_size, sh_degree, grid_min, grid_radius, dsh, ddensity, stream);
 }
 
 int ngp_voxel_occ_scratch_doubles(void) { return 2 * VOX_OCC_BLOCKS; }
